@@ -26,7 +26,8 @@ pages from a large stretch of device memory, which is what HBM wants for the ste
 of --placement-candidates (default 3) such buffer sets the fastest is kept; both are allocation choices, results never depend
 on them.
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  `--dump-outputs DIR` also writes what the last timed step computed (a fixed seeded sample of envs)
+as DIR/<name>.npy, so that two builds can be compared output for output: the inputs are the same from run to run.
 """
 from __future__ import annotations
 
@@ -210,7 +211,69 @@ def parse_args(argv):
                     help="N>1 only: extra legs of this many steps with the RCCL all-gather of the packed observation image")
     ap.add_argument("--gather-wire", choices=["f32", "native"], default="native",
                     help="observation dtype on the wire in the gather legs (f32 halves the bytes of float64 observations)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step computed as DIR/<name>.npy (rank 0; a fixed seeded sample "
+                         "of envs, at most 64 MB): dump_outputs()")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, shards, extra=None):
+    """--dump-outputs: the arrays the last step of the timed region handed its caller (BatchedPredPreyGrass.step_batch: observations,
+    rewards, terminated / truncated flags, live mask, agent ids), one DIR/<name>.npy each.  `shards` = [(first global env index, env)]
+    in env order.  Integers and float64 data are written as float64, everything else as float32.  Rows not in use are zeroed: their
+    buffers hold whatever an earlier step left there.  The envs are a fixed seeded sample, as many as fit in 64 MB (`env_index.npy`:
+    their indices on this rank), so runs with the same arguments write the same files.  `extra` = {name: tensor [B, ...]} of further
+    per-env outputs of the path."""
+    import numpy as np
+    import torch
+    from predpreygrass_amd import _abi
+    e0 = shards[0][1]
+    n_envs = sum(e.batch_size for _, e in shards)
+    f_obs = np.float64 if e0.obs_pred.dtype == torch.float64 else np.float32
+    f_rew = np.float64 if e0.row_reward.dtype == torch.float64 else np.float32
+    per_env = (e0.obs_pred[0].numel() + e0.obs_prey[0].numel()) * np.dtype(f_obs).itemsize + e0.S * (np.dtype(f_rew).itemsize + 3 * 4 + 8) \
+        + sum(t[0].numel() * 8 for t in (extra or {}).values()) + 8
+    n = min(n_envs, DUMP_BUDGET_BYTES // per_env)
+    if n < 1:
+        raise SystemExit(f"bench.py: one env's outputs ({per_env} bytes) exceed the {DUMP_BUDGET_BYTES}-byte budget of --dump-outputs")
+    idx = np.arange(n_envs) if n == n_envs else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_envs, n, replace=False))
+    parts = {}
+    for lo, e in shards:
+        mine = idx[(idx >= lo) & (idx < lo + e.batch_size)] - lo
+        if not len(mine):
+            continue
+        sel = torch.from_numpy(mine).to(e.device)
+        take = lambda t: t.index_select(0, sel).cpu()
+        es = take(e.env_state)
+        n_pred = es[:, _abi.ENV_N_PRED_ROWS:_abi.ENV_N_PRED_ROWS + 1].long()
+        n_prey = es[:, _abi.ENV_N_PREY_ROWS:_abi.ENV_N_PREY_ROWS + 1].long()
+        slot = torch.arange(e.S).unsqueeze(0)
+        live = torch.where(slot < e.pred_capacity, slot < n_pred, slot - e.pred_capacity < n_prey)
+        flags = take(e.row_flags).long()
+        obs_pred, obs_prey = take(e.obs_pred).double(), take(e.obs_prey).double()
+        obs_pred[~live[:, :e.pred_capacity]] = 0
+        obs_prey[~live[:, e.pred_capacity:]] = 0
+        got = {"obs_pred": obs_pred.numpy().astype(f_obs), "obs_prey": obs_prey.numpy().astype(f_obs),
+               "reward": torch.where(live, take(e.row_reward).double(), 0.0).numpy().astype(f_rew),
+               "terminated": (((flags & _abi.ROW_DIED) != 0) & live).numpy().astype(np.float32),
+               "truncated": (((flags & _abi.ROW_TRUNC) != 0) & live).numpy().astype(np.float32),
+               "live_mask": live.numpy().astype(np.float32),
+               "agent_id": torch.where(live, take(e.row_id).long(), -1).numpy().astype(np.float64)}
+        for name, t in (extra or {}).items():
+            got[name] = take(t[lo:lo + e.batch_size]).double().numpy()
+        for name, a in got.items():
+            parts.setdefault(name, []).append(a)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: np.concatenate(a) for name, a in parts.items()}
+    arrays["env_index"] = idx.astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 def dict_api(args, backend, device):
@@ -398,6 +461,8 @@ def policy_rollout(args, backend, device, distributed, rank, n_gpus):
         t = torch.tensor([wall], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [(0, env)], extra={"actions": scratch_actions[0] if args.policy_open_loop else env.actions})
     es = env.env_state.cpu().numpy().astype("int64")
     n_pred, n_prey = int(es[:, _abi.ENV_OBS_PRED].sum()), int(es[:, _abi.ENV_OBS_PREY].sum())
     # second leg (untimed for `value`): the policy kernels' own time, HIP events around every policy call of up to 100 more steps
@@ -518,6 +583,8 @@ def main(argv=None, backend=None):
     if args.workload == "dict_api":
         if distributed:
             raise SystemExit("bench.py: --workload dict_api is a one-process leg")
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs is not available for --workload dict_api (its steps run for a fixed time)")
         return dict_api(args, backend, device)
     rq = args.workload in ("red_queen", "walls")
     extra_kw = {}
@@ -673,6 +740,8 @@ def main(argv=None, backend=None):
     es = np.concatenate([e.env_state.cpu().numpy() for e in group.subs]).astype("int64")
     calls0 = np.concatenate([c.cpu().numpy() for c in calls0])
     assert ((es[:, _abi.ENV_CALLS] - calls0) == args.steps).all()
+    if args.dump_outputs and rank == 0 and not args.traffic_child:
+        dump_outputs(args.dump_outputs, [(lo, e) for (lo, _), e in zip(group.offsets, group.subs)])
 
     # ---- second leg: the same loop for --sustained-steps more steps, HIP events on the launch streams -------------------------
     # (the driver's 20-step window is 1.4 ms long: first-kernel latency and the drain of the last launches are 6-7 % of it; this leg

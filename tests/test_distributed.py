@@ -279,6 +279,55 @@ def test_bench_two_ranks_dry_run_with_gather_leg(launcher):
         assert len(d[leg]["per_rank_ms_per_step"]) == 2
 
 
+def test_bench_dump_outputs_dry_run(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's outputs as float32 / float64 .npy files, identical from two runs with the same
+    arguments; rows not in use are zeroed."""
+    args = ["--gpus", "1", "--steps", "4", "--warmup", "1", "--envs", "5", "--streams", "2", "--preroll-min", "64", "--preroll-max", "64"]
+    a, b = tmp_path / "a", tmp_path / "b"
+    d = _run_bench(args + ["--dump-outputs", str(a)], 1)
+    _run_bench(args + ["--dump-outputs", str(b)], 1)
+    assert d["steps"] == 4 and d["ms_per_step"] > 0
+    names = sorted(p.name for p in a.iterdir())
+    assert names == sorted(p.name for p in b.iterdir())
+    assert set(names) == {f"{n}.npy" for n in ("obs_pred", "obs_prey", "reward", "terminated", "truncated", "live_mask", "agent_id",
+                                               "env_index")}
+    got = {n[:-4]: np.load(a / n) for n in names}
+    for n in names:
+        assert got[n[:-4]].dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(got[n[:-4]], np.load(b / n))
+    assert list(got["env_index"]) == [0, 1, 2, 3, 4] and got["live_mask"].shape[0] == 5 and got["live_mask"].sum() > 0
+    cp = got["obs_pred"].shape[1]
+    assert not got["obs_pred"][got["live_mask"][:, :cp] == 0].any() and not got["obs_prey"][got["live_mask"][:, cp:] == 0].any()
+    assert got["obs_pred"][got["live_mask"][:, :cp] == 1].any()
+    assert (got["agent_id"][got["live_mask"] == 0] == -1).all()
+
+
+def test_bench_dump_outputs_samples_envs_within_the_budget(tmp_path, monkeypatch):
+    """More envs than fit in the budget: a fixed seeded sample, taken across sub-batches by global env index."""
+    import bench
+    from predpreygrass_amd.batched import BatchedPredPreyGrass
+    from predpreygrass_amd.config import config_env
+    lib = emu_backend.library()
+    subs = [BatchedPredPreyGrass(config_env, batch_size=n, seed=s, _library=lib) for n, s in ((3, 11), (4, 14))]
+    for e in subs:
+        e.reset()
+        for _ in range(5):
+            e.step(random_actions=True, auto_reset=True)
+    shards = [(0, subs[0]), (3, subs[1])]
+    names = bench.dump_outputs(str(tmp_path / "full"), shards)
+    full = {n: np.load(tmp_path / "full" / f"{n}.npy") for n in names}
+    per_env = sum(v[0].nbytes for k, v in full.items() if k != "env_index") + 8
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 3 * per_env + 100)
+    bench.dump_outputs(str(tmp_path / "part"), shards)
+    part = {n: np.load(tmp_path / "part" / f"{n}.npy") for n in names}
+    idx = part["env_index"].astype(np.int64)
+    assert len(idx) == 3 and list(idx) == sorted(set(idx)) and idx.max() < 7
+    assert sum(v.nbytes for v in part.values()) <= 3 * per_env + 100
+    for n in names:
+        if n != "env_index":
+            np.testing.assert_array_equal(part[n], full[n][idx])
+
+
 def test_bench_refuses_a_world_size_that_contradicts_gpus():
     import subprocess
     env = dict(os.environ, PYTHONPATH=ROOT, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
