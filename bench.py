@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the batched PredPreyGrass step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
-    python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+    python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is ONE batched call of the hot path: every env of the shard advances by one
 transition (predpreygrass_rllib_env.py:219-473 of the reference) -- device-side uniform random
@@ -18,9 +18,7 @@ agents and a step writes 2.7x fewer observation bytes than the workload defines)
 
 N GPUs = N independent shards of 4096 envs (weak scaling, no data-path collective: envs never
 interact).  `python bench.py --gpus N` without a torch.distributed launcher starts the N ranks itself.
-For N>1 two extra legs measure the step followed by the ONE RCCL all-gather of the packed observation
-image that north_star specifies ("obs_gather", "obs_gather_overlapped"; bandwidth-bound on xGMI, see
-DESIGN.md).  Within one GPU the 4096 envs are stepped as --streams (default 3) independent sub-batches on
+Within one GPU the 4096 envs are stepped as --streams (default 3) independent sub-batches on
 separate HIP streams.  Their observation tensors are allocated with ppg_alloc_spread (--obs-spread, default 32: physical
 pages from a large stretch of device memory, which is what HBM wants for the step's scattered writes -- profiles/EXPERIMENTS.md, round 3), and
 of --placement-candidates (default 3) such buffer sets the fastest is kept; both are allocation choices, results never depend
@@ -28,6 +26,13 @@ on them.
 
 Prints ONE JSON line (rank 0).  `--dump-outputs DIR` also writes what the last timed step computed (a fixed seeded sample of envs)
 as DIR/<name>.npy, so that two builds can be compared output for output: the inputs are the same from run to run.
+
+A plain run does what `value` and `ms_per_step` need and nothing more: set-up, pre-roll, warm-up, the timed steps, the outputs
+of --dump-outputs, the result line.  `--full` adds every leg that measures something else, after the timed region or in processes
+of its own: the HBM traffic from PMC passes of the same command (`roofline.traffic`), clocks and power under load, a sustained leg
+(`roofline.kernel_ms_sustained`), the fused rollout, for N>1 the legs with the ONE RCCL all-gather of the packed observation image
+that north_star specifies ("obs_gather", "obs_gather_overlapped", ...; bandwidth-bound on xGMI), and the CPU
+baseline; likewise the other workloads' second legs and CPU baselines.  The options of those legs take effect with --full.
 """
 from __future__ import annotations
 
@@ -138,6 +143,10 @@ def parse_args(argv):
     ap.add_argument("--warmup", type=int, default=300)
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region (and in child processes of their own) also run every leg that measures something other "
+                         "than `value`: PMC traffic, device state under load, sustained and fused legs, the gather legs (N>1), the CPU "
+                         "baseline, the other workloads' second legs.  Without it a run does only what `value` and ms_per_step need")
     ap.add_argument("--obs-dtype", choices=["f64", "f32", "bf16"], default=None,
                     help="observation dtype (default: f64 for the base workload, f32 -- the reference's -- for red_queen, bf16 -- the "
                          "compact rows the policy kernels stage without conversion -- for policy_rollout)")
@@ -158,9 +167,9 @@ def parse_args(argv):
     ap.add_argument("--policy-open-loop", action="store_true",
                     help="policy_rollout, timing experiments only: the policy's actions go to a scratch tensor and the envs are stepped with "
                          "device-side random actions -- the population then does not depend on what the (possibly ablated) kernels compute")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=8.0,
-                    help="cpu_baseline: wall seconds of the all-cores leg (a single-thread leg of a third of that runs first)")
+                    help="--full, cpu_baseline: wall seconds of the all-cores leg (a single-thread leg of a third of that runs first)")
     ap.add_argument("--streams", type=int, default=None,
                     help="independent sub-batches per GPU, each on its own HIP stream (1 = one launch per step).  2 vs 3 with the "
                          "cooperative kernels, us per 4096-env step in one gpurun call each: GPU in its fast state 68.3 / 71.2, 67.2 / "
@@ -168,7 +177,7 @@ def parse_args(argv):
                          "Default: 3; the walls and drive workloads 2 (their kernels are bound by per-env work, not by the write streams: "
                          "92.3 vs 94.9 and 180.1 vs 183.3 us per step, profiles/r05/l_walls_drive_pair_kernels_ab.txt)")
     ap.add_argument("--sustained-steps", type=int, default=2000,
-                    help="after the timed region: a second leg of this many steps timed with HIP events on the launch streams "
+                    help="--full: after the timed region a second leg of this many steps timed with HIP events on the launch streams "
                          "(roofline.kernel_ms_sustained); 0 = skip")
     ap.add_argument("--wave-plan", default=None,
                     help="A/B experiments: 'waves,helper_min_rows,coop_envs' forced on every sub-batch (ppg_set_wave_plan); the default is "
@@ -184,7 +193,7 @@ def parse_args(argv):
                     help="the pre-roll continues in 64-step windows until the mean rows per env of two consecutive windows "
                          "differ by < 1 %%, at most this many steps (0 = no pre-roll: measures the post-reset transient)")
     ap.add_argument("--fused-steps", type=int, default=100,
-                    help="third leg (headline workload on a cooperative plan): ppg_rollout with this many transitions per launch, for as "
+                    help="--full: third leg (headline workload on a cooperative plan): ppg_rollout with this many transitions per launch, for as "
                          "many steps as the sustained leg (reported as `fused_rollout`, never as `value`); 0 = skip")
     ap.add_argument("--device-warm-seconds", type=float, default=2.0,
                     help="before the pre-roll the envs are stepped for this long (wall clock) and then reset again: a GPU that has been idle needs about a second of "
@@ -201,20 +210,23 @@ def parse_args(argv):
                          "profiles/r03/e_placement_experiments.txt); the constructor builds K candidate buffer sets side by side, steps each for "
                          "~70 ms and keeps the fastest (0.6 s and 14 GB of transient memory at K = 8).  1 = take the first allocation as it comes")
     ap.add_argument("--measure-traffic", dest="measure_traffic", action="store_true", default=None,
-                    help="roofline.traffic from PMC passes of this command on THIS box (two child runs under rocprofv3 --pmc, ~25 s); "
-                         "default: on for the single-GPU headline workload, off otherwise")
+                    help="--full: roofline.traffic from PMC passes of this command on THIS box (two child runs under rocprofv3 --pmc, "
+                         "~25 s); default: on for the single-GPU headline workload, off otherwise")
     ap.add_argument("--no-measure-traffic", dest="measure_traffic", action="store_false")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--force-dist", action="store_true",
-                    help="initialise torch.distributed even for one rank, so that the gather legs run (needs torchrun)")
+                    help="initialise torch.distributed even for one rank, so that the gather legs of --full run (needs torchrun)")
     ap.add_argument("--gather-steps", type=int, default=50,
-                    help="N>1 only: extra legs of this many steps with the RCCL all-gather of the packed observation image")
+                    help="--full, N>1 only: extra legs of this many steps with the RCCL all-gather of the packed observation image")
     ap.add_argument("--gather-wire", choices=["f32", "native"], default="native",
                     help="observation dtype on the wire in the gather legs (f32 halves the bytes of float64 observations)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed region, write what its last step computed as DIR/<name>.npy (rank 0; a fixed seeded sample "
                          "of envs, at most 64 MB): dump_outputs()")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.measure_traffic and not args.full:
+        ap.error("--measure-traffic is a leg of --full")
+    return args
 
 
 DUMP_BUDGET_BYTES = 64_000_000
@@ -280,8 +292,9 @@ def dict_api(args, backend, device):
     """`--workload dict_api`: what a script gets that only changes its import (BASE:219,473; one env per runner, TUNE:179-185).
     Leg 1: `PredPreyGrass(config)` -- reset(seed), then step(action_dict) with host-side random actions for every live agent (the protocol
     of random_policy.py / SURVEY Appendix B), reset again when the episode ends.  Leg 2: `VectorPredPreyGrass(64)`, one action dict per
-    env, auto-reset.  Leg 3 (comparison): leg 1's loop with the data movement of rounds 1-4 -- one host->device copy of the actions, ten
-    `.cpu()` copies of the tables and two of the observation slabs per call -- behind the same dict assembly."""
+    env, auto-reset.  Leg 3 (comparison, --full only): leg 1's loop with the data movement of rounds 1-4 -- one host->device copy of the
+    actions, ten `.cpu()` copies of the tables and two of the observation slabs per call -- behind the same dict assembly.  Leg 1 runs
+    in every run: it warms the process up for leg 2 and its rate is the basis of the line's roofline figure."""
     import numpy as np
     import torch
     from predpreygrass_amd import _abi
@@ -324,7 +337,7 @@ def dict_api(args, backend, device):
     one = PredPreyGrass(cfg, device=None if dry else device, **lib_kw)
     drive_one(one, lambda e, a: e.step(a), seconds / 4)   # warm-up
     rate_one, agents_one = drive_one(one, lambda e, a: e.step(a), seconds)
-    rate_legacy, _ = drive_one(one, legacy_step, seconds / 2)
+    rate_legacy = drive_one(one, legacy_step, seconds / 2)[0] if args.full else None
     nv = 4 if dry else 64
     vec = VectorPredPreyGrass(cfg, num_envs=nv, device=None if dry else device, seed=args.seed, auto_reset=True, **lib_kw)
     res = vec.reset(seed=args.seed)
@@ -352,9 +365,10 @@ def dict_api(args, backend, device):
                          "copy (ppg_fetch), the reference's dicts rebuilt in Python"),
             "single_env": {"calls_per_s": round(rate_one, 1), "us_per_call": round(us_one, 1), "mean_agents_per_call": round(agents_one, 1),
                            "what": "PredPreyGrass(config).reset(seed) / .step(action_dict), one env (what one RLlib env runner holds, TUNE:179-185)"},
-            "single_env_rounds_1_to_4_data_movement": {"calls_per_s": round(rate_legacy, 1), "us_per_call": round(1e6 / rate_legacy, 1),
-                                                       "what": "the same loop with thirteen synchronous copies per call (ten table .cpu(), two observation slabs, one action row)"},
-            "speedup_vs_rounds_1_to_4": round(rate_one / rate_legacy, 2),
+            **({"single_env_rounds_1_to_4_data_movement": {
+                    "calls_per_s": round(rate_legacy, 1), "us_per_call": round(1e6 / rate_legacy, 1),
+                    "what": "the same loop with thirteen synchronous copies per call (ten table .cpu(), two observation slabs, one action row)"},
+                "speedup_vs_rounds_1_to_4": round(rate_one / rate_legacy, 2)} if rate_legacy is not None else {}),
             "vector_env": {"envs": nv, "env_steps_per_s": round(rate_vec, 1), "calls_per_s": round(rate_vec / nv, 1)},
             "reference_python_fixed": "reference Python step(): 45 env-steps/s (default config) / 441 (C1) on 1 core, ~400 on 8 cores (BASELINE.md section 2)",
         },
@@ -363,7 +377,7 @@ def dict_api(args, backend, device):
                      "note": "a latency-bound path by construction (one env per call, PCIe round trip + Python dict assembly per call): the fraction "
                              "of the HBM peak is printed for the contract's sake and says nothing here; the HBM-bound figure is the default workload's"},
     }
-    if not args.no_cpu_baseline and not dry:
+    if args.full and not args.no_cpu_baseline and not dry:
         from oracle.ppg_oracle import OracleEnv
         env = OracleEnv(cfg)
         t0, steps = time.perf_counter(), 0
@@ -382,7 +396,7 @@ def policy_rollout(args, backend, device, distributed, rank, n_gpus):
     """`--workload policy_rollout`: every step = ppg_policy_act (both species' networks of tune_ppo_base_environment.py:106-141,
     random-initialised weights, actions sampled from the softmax) + ppg_step with those actions, auto-reset.  Not the headline
     config: the same envs with the policy closed around them on the device.  Roofline: bf16 MFMA, real (unpadded) flops of
-    the six layers over the policy kernels' time (HIP events around ppg_policy_act on the launch stream)."""
+    the six layers over the policy kernels' time (--full: HIP events around ppg_policy_act on the launch stream in a second leg)."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -465,18 +479,20 @@ def policy_rollout(args, backend, device, distributed, rank, n_gpus):
         dump_outputs(args.dump_outputs, [(0, env)], extra={"actions": scratch_actions[0] if args.policy_open_loop else env.actions})
     es = env.env_state.cpu().numpy().astype("int64")
     n_pred, n_prey = int(es[:, _abi.ENV_OBS_PRED].sum()), int(es[:, _abi.ENV_OBS_PREY].sum())
-    # second leg (untimed for `value`): the policy kernels' own time, HIP events around every policy call of up to 100 more steps
-    ev_steps = min(args.steps, 100)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(ev_steps)]
-    for k in range(ev_steps):
-        one_step(evs[k])
-    torch.cuda.synchronize(device)
-    pol_ms = sum(a.elapsed_time(b) for a, b in evs) / ev_steps * args.steps   # (scaled to the timed region's step count)
-    es2 = env.env_state.cpu().numpy().astype("int64")
-    ev_pred, ev_prey = int(es2[:, _abi.ENV_OBS_PRED].sum()) - n_pred, int(es2[:, _abi.ENV_OBS_PREY].sum()) - n_prey
     flops = 2.0 * (n_pred * fused.macs_per_observation(0) + n_prey * fused.macs_per_observation(1))
-    ev_flops = 2.0 * (ev_pred * fused.macs_per_observation(0) + ev_prey * fused.macs_per_observation(1))
-    achieved = ev_flops / (pol_ms / args.steps * ev_steps * 1e-3) / 1e12
+    # --full, second leg (untimed for `value`): the policy kernels' own time, HIP events around every policy call of up to 100 more steps
+    ev_steps = min(args.steps, 100)
+    pol_ms = ev_flops = achieved = None
+    if args.full:
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(ev_steps)]
+        for k in range(ev_steps):
+            one_step(evs[k])
+        torch.cuda.synchronize(device)
+        pol_ms = sum(a.elapsed_time(b) for a, b in evs) / ev_steps * args.steps   # (scaled to the timed region's step count)
+        es2 = env.env_state.cpu().numpy().astype("int64")
+        ev_pred, ev_prey = int(es2[:, _abi.ENV_OBS_PRED].sum()) - n_pred, int(es2[:, _abi.ENV_OBS_PREY].sum()) - n_prey
+        ev_flops = 2.0 * (ev_pred * fused.macs_per_observation(0) + ev_prey * fused.macs_per_observation(1))
+        achieved = ev_flops / (pol_ms / args.steps * ev_steps * 1e-3) / 1e12
     if rank == 0:
         out = {
             "metric": "env-steps/sec at 4096x(25x25) grids, 1/2/4/8 MI355X; % HBM roofline",
@@ -494,23 +510,24 @@ def policy_rollout(args, backend, device, distributed, rank, n_gpus):
                 **({"open_loop": "TIMING EXPERIMENT: the envs were stepped with random actions, the policy's actions discarded"} if args.policy_open_loop else {}),
                 "bytes_per_agent_a_consumer_has_to_move": 1,
             },
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": None,
+            "roofline": {"bound": "mfma", "achieved": None if achieved is None else round(achieved, 1), "peak": MFMA_BF16_PEAK_TFLOPS,
+                         "unit": "TFLOP/s", "frac": None if achieved is None else round(achieved / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": None,
                          "kernel": {"rllib": "ppg_policy_pipe2_16_8_" if os.environ.get("PPG_POLICY_FUSED", "1") != "0" else "ppg_policy_pipe{8,16}_", "depth": "ppg_policy_pipe8_ (predators) + ppg_policy_deep16_ (prey) "}.get(args.policy_arch, "ppg_policy_forward_") + args.obs_dtype,
                          "policy_arch": args.policy_arch,
                          "macs_per_observation": [fused.macs_per_observation(0), fused.macs_per_observation(1)],
-                         "kernel_ms": round(pol_ms / args.steps, 5),
+                         "kernel_ms": None if pol_ms is None else round(pol_ms / args.steps, 5),
                          "kernel_ms_leg": f"a SECOND leg of {ev_steps} steps with HIP events around every policy call (an event record between two "
                                           "kernels costs ~5 us of idle GPU, so the timed region has none): kernel_ms, achieved and frac come "
-                                          "from it and its own observation counts; value and ms_per_step from the event-free timed region",
+                                          "from it and its own observation counts (--full only); value and ms_per_step from the event-free "
+                                          "timed region",
                          "flops_per_step": int(flops / args.steps),
-                         "flops_per_step_event_leg": int(ev_flops / ev_steps),
+                         "flops_per_step_event_leg": None if ev_flops is None else int(ev_flops / ev_steps),
                          "note": "flops = 2 x multiply-accumulates of the network's layers (no padding counted) x observations evaluated; "
                                  "kernel_ms = the policy's launch(es) per step: ONE fused launch for both species (ppg_policy_pipe2_*; "
                                  "PPG_POLICY_FUSED=0: a plan launch + one forward launch per species)"},
         }
         out.update(per_rank_summary(per_rank, n_gpus, B))
-        if not args.no_cpu_baseline and n_gpus == 1:
+        if args.full and not args.no_cpu_baseline and n_gpus == 1:
             n_threads = min(os.cpu_count() or 1, 32)   # (more threads than that make these small convolutions slower, not faster)
             torch.set_num_threads(n_threads)
             x = [torch.rand(2048, 4, env.Rp, env.Rp), torch.rand(2048, 4, env.Rq, env.Rq)]
@@ -547,19 +564,19 @@ def main(argv=None, backend=None):
     world = int(env_world or "1")
     if env_world is not None and world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
-    # PMC passes of this command in child processes, before this process touches the GPU (single-GPU headline workload only)
+    # --full: PMC passes of this command in child processes, before this process touches the GPU (single-GPU headline workload only)
     pmc = None
     want_pmc = args.measure_traffic if args.measure_traffic is not None else (args.workload == "base" and args.envs == 4096)
-    if want_pmc and not args.traffic_child and world == 1 and not args.force_dist and not (backend and backend.dry):
+    if args.full and want_pmc and not args.traffic_child and world == 1 and not args.force_dist and not (backend and backend.dry):
         pmc = measure_traffic(argv, args, __file__)
 
     # clocks / power / who else is on the GPU while the loop runs: a side process, started before this one touches the GPU
-    sampler = (None, "not started: dry run, a rank other than 0, a PMC child run or no sustained leg")
+    sampler = (None, "not started: a run without --full, dry run, a rank other than 0, a PMC child run or no sustained leg")
     # (not under rocprofv3: its preloaded tool library has initialised the GPU in THIS process before main() runs, so starting the
     #  side process here would already be an exec from a GPU-initialised process)
     profiler_attached = any(k.startswith(("ROCPROF", "ROCP_", "ROCTRACER", "HSA_TOOLS")) for k in os.environ)
-    if not (backend and backend.dry) and int(os.environ.get("RANK", "0")) == 0 and not args.traffic_child and args.sustained_steps > 0 \
-            and args.workload not in ("policy_rollout", "dict_api"):
+    if args.full and not (backend and backend.dry) and int(os.environ.get("RANK", "0")) == 0 and not args.traffic_child \
+            and args.sustained_steps > 0 and args.workload not in ("policy_rollout", "dict_api"):
         sampler = (None, "not started: a profiler is attached to this process") if profiler_attached else start_state_sampler()
 
     import numpy as np
@@ -747,7 +764,7 @@ def main(argv=None, backend=None):
     # (the driver's 20-step window is 1.4 ms long: first-kernel latency and the drain of the last launches are 6-7 % of it; this leg
     # says what the same kernel does back to back.  Not `value`: the driver asked for exactly --steps steps.)
     sustained = None
-    if args.sustained_steps > 0 and not dry:
+    if args.full and args.sustained_steps > 0 and not dry:
         s0 = [backend.event() for _ in group.streams]
         s1 = [backend.event() for _ in group.streams]
         backend.synchronize(device)
@@ -765,8 +782,9 @@ def main(argv=None, backend=None):
                      "ms_per_step": ts / args.sustained_steps * 1e3}
 
     # clocks / power / temperatures WHILE the same loop runs (untimed extra steps on rank 0 for as long as one rocm-smi call takes)
-    dev_state = {"unavailable": "not sampled: " + ("dry run" if dry else "not rank 0" if rank != 0 else "PMC child run" if args.traffic_child
-                                                   else "--sustained-steps 0" if args.sustained_steps <= 0 else str(sampler[1]))}
+    dev_state = {"unavailable": "not sampled: " + ("a run without --full" if not args.full else "dry run" if dry else "not rank 0" if rank != 0
+                                                   else "PMC child run" if args.traffic_child else "--sustained-steps 0" if args.sustained_steps <= 0
+                                                   else str(sampler[1]))}
     # (never under a profiler: its preloaded library initialises the GPU in every child process, and rocm-smi is a `#!/usr/bin/env python3`
     #  script -- an exec from a GPU-initialised process, which the GPU boxes refuse)
     under_profiler = bool(os.environ.get("LD_PRELOAD")) or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
@@ -796,7 +814,7 @@ def main(argv=None, backend=None):
             dev_state = got
         else:
             dev_state = {"unavailable": "the side sampler (rocm-smi in a process started before the GPU was touched) produced no whole sample in 6 s of stepping"}
-    elif not dry and rank == 0 and not args.traffic_child and args.sustained_steps > 0 and not under_profiler:
+    elif args.full and not dry and rank == 0 and not args.traffic_child and args.sustained_steps > 0 and not under_profiler:
         import threading
         box = {}
         th = threading.Thread(target=lambda: box.update(state=device_state()))
@@ -812,7 +830,7 @@ def main(argv=None, backend=None):
     # written every step exactly as above (bit-identical to n ppg_step calls; tests).  Reported next to `value`, never as `value`:
     # `value` is the per-step API, which also takes actions from outside.
     fused = None
-    if args.fused_steps > 0 and not dry and args.workload in ("base", "red_queen") and group.subs[0].wave_plan()[2] > 0 \
+    if args.full and args.fused_steps > 0 and not dry and args.workload in ("base", "red_queen") and group.subs[0].wave_plan()[2] > 0 \
             and group.subs[0].wave_plan()[0] == 4:
         n_f = args.fused_steps
         launches = max(1, args.sustained_steps // n_f) if args.sustained_steps > 0 else 4
@@ -854,7 +872,7 @@ def main(argv=None, backend=None):
     # ---- optional legs: the ONE RCCL all-gather per step north_star specifies (N > 1 only) -------------------------
     gather_info = gather_overlapped = None
     extra_legs = {}
-    if distributed and args.gather_steps > 0:
+    if args.full and distributed and args.gather_steps > 0:
         from predpreygrass_amd.distributed import ObservationGatherer
         wire = torch.float32 if args.gather_wire == "f32" else None
         rows_now = (es[:, _abi.ENV_N_PRED_ROWS].mean(), es[:, _abi.ENV_N_PREY_ROWS].mean())
@@ -1075,7 +1093,7 @@ def main(argv=None, backend=None):
             out["obs_gather_overlapped"] = gather_overlapped
         if gather_info is not None:
             out.update(extra_legs)
-        if not args.no_cpu_baseline and not dry:   # rank 0's host cores, also next to the N > 1 curve (north_star)
+        if args.full and not args.no_cpu_baseline and not dry:   # rank 0's host cores, also next to the N > 1 curve (north_star)
             out["cpu_baseline"] = cpu_baseline(cfg, args.seed, seconds=args.cpu_seconds, workload=args.workload)
         print(json.dumps(out), flush=True)
     if distributed:

@@ -189,9 +189,8 @@ def measure_traffic(argv, args, bench_path, timeout=240):
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe):
         return None
-    child_args = [a for a in argv if a not in ("--measure-traffic",)]
-    child_args += ["--no-cpu-baseline", "--sustained-steps", "0", "--fused-steps", "0", "--traffic-child", "--device-warm-seconds", "0.5",
-                   "--placement-candidates", "1", "--obs-spread", "0"]
+    child_args = [a for a in argv if a not in ("--measure-traffic", "--full")]   # (the child runs the timed region and nothing else)
+    child_args += ["--traffic-child", "--device-warm-seconds", "0.5", "--placement-candidates", "1", "--obs-spread", "0"]
     out = {}
     tmp = tempfile.mkdtemp(prefix="ppg_pmc_", dir=os.environ.get("TMPDIR", "/tmp"))
     try:

@@ -259,7 +259,7 @@ def test_bench_two_ranks_dry_run_with_gather_leg(launcher):
     """`torch.distributed.run --nproc-per-node 2 bench.py --gpus 2` as the driver launches it, and plain
     `bench.py --gpus 2` (which starts its two ranks itself), gloo on CPU: barrier + max-over-ranks timing, rank-0 JSON,
     the single-collective obs_gather legs."""
-    d = _run_bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--envs", "5", "--streams", "2",
+    d = _run_bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--envs", "5", "--streams", "2", "--full",
                     "--gather-steps", "3", "--preroll-min", "64", "--preroll-max", "64"], 2, launcher=launcher)
     assert d["n_gpus"] == 2 and d["config"]["envs_per_gpu"] == 5
     for leg in ("obs_gather", "obs_gather_overlapped", "obs_gather_to_root", "obs_all_pairs", "ids_rewards_gather"):
@@ -277,6 +277,35 @@ def test_bench_two_ranks_dry_run_with_gather_leg(launcher):
     assert d["value_if_every_rank_were_median"] >= d["value"] * 0.999 and d["slowest_over_median_rank"] >= 1.0
     for leg in ("obs_gather", "obs_all_pairs", "ids_rewards_gather"):
         assert len(d[leg]["per_rank_ms_per_step"]) == 2
+
+
+def test_bench_plain_run_leaves_the_other_legs_to_full(monkeypatch):
+    """Without --full a run measures `value` and nothing else: no gather legs for N>1 (the same command with --full has them:
+    test_bench_two_ranks_dry_run_with_gather_leg), no sustained leg, no device-state sampling; --measure-traffic asks for --full,
+    and the PMC child runs of --full time the plain command."""
+    import shutil
+    import subprocess
+    import types
+    import bench
+    import bench_support
+    d = _run_bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--envs", "5", "--streams", "2",
+                    "--gather-steps", "3", "--preroll-min", "64", "--preroll-max", "64"], 2, launcher=False)
+    assert d["n_gpus"] == 2 and d["steps"] == 5 and d["ms_per_step"] > 0 and [r["rank"] for r in d["per_rank"]] == [0, 1]
+    assert not {"obs_gather", "obs_gather_overlapped", "obs_gather_to_root", "obs_all_pairs", "ids_rewards_gather",
+                "fused_rollout", "cpu_baseline"} & set(d)
+    assert d["roofline"]["kernel_ms_sustained"] is None
+    assert "without --full" in d["config"]["device_state_under_load"]["unavailable"]
+    assert not bench.parse_args([]).full and bench.parse_args(["--full"]).full
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--measure-traffic"])
+    cmds = []
+    monkeypatch.setattr(shutil, "which", lambda name: sys.executable)
+    monkeypatch.setattr(subprocess, "run", lambda cmd, **kw: cmds.append(cmd) or types.SimpleNamespace(returncode=1, stdout="", stderr=""))
+    argv = ["--steps", "20", "--warmup", "5", "--full", "--measure-traffic"]
+    assert bench_support.measure_traffic(argv, bench.parse_args(argv), bench.__file__) is None
+    child = cmds[0][cmds[0].index(os.path.abspath(bench.__file__)) + 1:]
+    assert child[:4] == ["--steps", "20", "--warmup", "5"] and "--traffic-child" in child
+    assert "--full" not in child and "--measure-traffic" not in child
 
 
 def test_bench_dump_outputs_dry_run(tmp_path):

@@ -405,7 +405,7 @@ def test_bench_rccl_gather_legs_with_one_rank():
     def run(port, timeout):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "200", "--warmup", "50",
-               "--envs", "1024", "--force-dist", "--no-cpu-baseline", "--gather-steps", "5", "--preroll-max", "400"]
+               "--envs", "1024", "--force-dist", "--full", "--no-cpu-baseline", "--gather-steps", "5", "--preroll-max", "400"]
         return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=root)
     try:
         out = run(29533, 420)   # (takes ~10 s)

@@ -3,15 +3,16 @@
 #   usage: tools/gpu_policy_ab.sh TAG ROUNDS name=path/to/lib.so [name=...]     (name "base" = the product library)
 cd "$GRAFT_REPO_ROOT" || exit 1
 tag=$1; rounds=$2; shift 2
-mkdir -p gpurun_out
-out=gpurun_out/${tag}_policy_ab.txt
+: "${OUT_DIR:?set OUT_DIR to the folder the outputs go to}"
+mkdir -p "$OUT_DIR"
+out=$OUT_DIR/${tag}_policy_ab.txt
 : > $out
 for r in $(seq 1 $rounds); do
   for spec in "$@"; do
     name=${spec%%=*}; lib=${spec#*=}
     if [ "$name" = base ]; then unset PPG_HIP_LIB; else export PPG_HIP_LIB=$PWD/$lib; fi
-    python3 bench.py --workload policy_rollout --steps 60 --warmup 10 --no-cpu-baseline > gpurun_out/${tag}_pab.json 2> gpurun_out/${tag}_pab.err
-    python3 - "$name" "$r" gpurun_out/${tag}_pab.json >> $out <<'PY'
+    python3 bench.py --workload policy_rollout --steps 60 --warmup 10 --no-cpu-baseline --full > $OUT_DIR/${tag}_pab.json 2> $OUT_DIR/${tag}_pab.err
+    python3 - "$name" "$r" $OUT_DIR/${tag}_pab.json >> $out <<'PY'
 import json, sys
 for l in open(sys.argv[3]):
     if l.startswith("{"):

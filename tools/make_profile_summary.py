@@ -2,19 +2,21 @@
 """Assemble profiles/<round>/bench_driver_summary.json from rocprofv3 runs of THE DRIVER'S bench command
 (`python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline`: untimed pre-roll to the steady state, 5 warm-up steps, 20 timed
 steps, then the sustained leg of 2000 steps; 3 sub-batches), taken on the GPU box by tools/gpu_profile_driver_cmd.sh:
-  rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/<tag>_trace -o t -- python3 bench.py <args>
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/<tag>_w -o w -- python3 bench.py <args>
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/<tag>_f -o f -- python3 bench.py <args>
-  python3 bench.py <args without --no-cpu-baseline> > gpurun_out/<tag>_bench.json        (unprofiled, same box)
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT_DIR/<tag>_trace -o t -- python3 bench.py <args> --full
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT_DIR/<tag>_w -o w -- python3 bench.py <args> --full
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT_DIR/<tag>_f -o f -- python3 bench.py <args> --full
+  python3 bench.py <args without --no-cpu-baseline> --full > $OUT_DIR/<tag>_bench.json        (unprofiled, same box)
 The sustained leg of each run = its last sustained x streams dispatches of the step kernel, the timed region = the steps x streams
 dispatches in front of them.
 usage: make_profile_summary.py <tag> <kernel name | auto = roofline.kernel of the bench line> <out.json> [steps=20] [streams=3] [sustained=2000]"""
 import csv
 import glob
 import json
+import os
 import sys
 
 tag, kernel, out = sys.argv[1], sys.argv[2], sys.argv[3]
+D = os.environ["OUT_DIR"]   # where the runs above wrote
 steps = int(sys.argv[4]) if len(sys.argv) > 4 else 20
 streams = int(sys.argv[5]) if len(sys.argv) > 5 else 3
 sustained = int(sys.argv[6]) if len(sys.argv) > 6 else 2000
@@ -29,7 +31,7 @@ def timed(v):      # the dispatches of the timed region
 def sust(v):       # the dispatches of the sustained leg
     return v[len(v) - tail:] if tail else []
 if kernel == "auto":
-    kernel = json.loads(open(f"gpurun_out/{tag}_bench.json").read().strip().splitlines()[-1])["roofline"]["kernel"]
+    kernel = json.loads(open(f"{D}/{tag}_bench.json").read().strip().splitlines()[-1])["roofline"]["kernel"]
 
 
 def one(pattern):
@@ -40,7 +42,7 @@ def one(pattern):
 
 durs = []
 info = {}
-for r in csv.DictReader(open(one(f"gpurun_out/{tag}_trace/**/*kernel_trace.csv"))):
+for r in csv.DictReader(open(one(f"{D}/{tag}_trace/**/*kernel_trace.csv"))):
     if r["Kernel_Name"] == kernel:
         durs.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]) - int(r["Start_Timestamp"])))
         info = {"grid_threads": int(r.get("Grid_Size_X", r.get("Grid_Size", 0)) or 0),
@@ -58,10 +60,10 @@ def pmc_mean(path, name):
     return sum(vals) / len(vals), len(vals)
 
 
-w, nw = pmc_mean(one(f"gpurun_out/{tag}_w/**/*counter_collection.csv"), "WRITE_SIZE")
-f, nf = pmc_mean(one(f"gpurun_out/{tag}_f/**/*counter_collection.csv"), "FETCH_SIZE")
-b = json.loads(open(f"gpurun_out/{tag}_bench.json").read().strip().splitlines()[-1])
-bt = json.loads(open(f"gpurun_out/{tag}_bench_under_trace.json").read().strip().splitlines()[-1])
+w, nw = pmc_mean(one(f"{D}/{tag}_w/**/*counter_collection.csv"), "WRITE_SIZE")
+f, nf = pmc_mean(one(f"{D}/{tag}_f/**/*counter_collection.csv"), "FETCH_SIZE")
+b = json.loads(open(f"{D}/{tag}_bench.json").read().strip().splitlines()[-1])
+bt = json.loads(open(f"{D}/{tag}_bench_under_trace.json").read().strip().splitlines()[-1])
 total = w * 1024 + 2 * f * 1024
 kernel_us = sum(timed(d)) / len(timed(d)) / 1e3
 kernel_us_sustained = sum(sust(d)) / len(sust(d)) / 1e3 if tail else None
