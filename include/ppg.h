@@ -113,7 +113,8 @@ typedef struct ppg_config {
     int32_t n_initial_predators;  /* BASE:46 */
     int32_t n_initial_prey;       /* BASE:47 */
     int32_t n_grass;              /* BASE:59 */
-    int32_t pred_capacity;        /* predator rows per env: 64 */
+    int32_t pred_capacity;        /* predator rows per env: 64, or 128 (one wave per env: no multi-wave or cooperative plan, no
+                                   * drive channels, no policy kernels; prey_capacity 128 or 256) */
     int32_t prey_capacity;        /* prey rows per env: 64, 128 or 256 */
     int32_t grass_capacity;       /* >= n_grass, multiple of 64 */
     int32_t obs_dtype;            /* 0: float64 (bit-exact with the reference), 1: float32, 2: bfloat16 (the float64 value rounded to
@@ -213,7 +214,7 @@ typedef struct ppg_config_gen2 {
     int32_t n_possible[4];        /* RQ:56-59, pool order; each <= 65535, sum <= 32767 */
     int32_t n_initial[4];         /* RQ:61-64 */
     int32_t n_grass;              /* RQ:76 */
-    int32_t pred_capacity;        /* 64 */
+    int32_t pred_capacity;        /* 64, or 128 without walls (one wave per env, prey_capacity 128 or 256: see ppg_config) */
     int32_t prey_capacity;        /* 64, 128 or 256 */
     int32_t grass_capacity;
     int32_t obs_dtype;            /* 0: float64, 1: float32 (the reference's dtype), 2: bfloat16, 3: bfloat16 cells (see ppg_config) */

@@ -17,7 +17,9 @@ from . import _abi
 from .config import resolve_config
 
 PREDATOR, PREY = 0, 1
-PRED_CAPACITY = 64
+PRED_CAPACITY = 64                # predator rows per env by default
+PRED_CAPACITIES = (64, 128)       # 128: one-wave kernels only -- base family (no drive channels) and second generation without walls,
+                                  # prey_capacity 128 or 256; no policy kernels (include/ppg.h: ppg_config.pred_capacity)
 
 
 def lexkey(ids) -> np.ndarray:
@@ -39,7 +41,8 @@ def agent_name(type_: int, id_: int) -> str:
 class BatchedPredPreyGrass:
     """Tensor API.
 
-    Rows: ``[0, 64)`` predators, ``[64, 64 + prey_capacity)`` prey.  Within a type the rows of
+    Rows: ``[0, pred_capacity)`` predators (``pred_capacity`` 64, or 128 with ``prey_capacity`` 128 or 256 and
+    one wave per env), ``[pred_capacity, pred_capacity + prey_capacity)`` prey.  Within a type the rows of
     the last call are ordered like the dict the reference's ``step()`` returns:
     survivors (incl. agents that died in that call) followed by newborns.  ``actions[b, row]``
     answers the observation in the same row of the previous call; rows that are dead, unused or
@@ -47,7 +50,7 @@ class BatchedPredPreyGrass:
     """
 
     def __init__(self, config=None, batch_size=1, device=None, obs_dtype=torch.float64,
-                 prey_capacity=128, seed=0, _library=None, obs_spread=0):
+                 prey_capacity=128, seed=0, _library=None, obs_spread=0, pred_capacity=PRED_CAPACITY):
         """obs_spread = N > 1: the two observation tensors live in memory from `ppg_alloc_spread` (include/ppg.h) -- physical pages
         picked at random from a stretch of device memory N times their size, which is what HBM wants for the step's scattered writes
         (profiles/EXPERIMENTS.md, round 3; N = 32 costs a few seconds and N x the tensors' size of transient device memory).  They stay valid
@@ -73,7 +76,7 @@ class BatchedPredPreyGrass:
             if len(lst) > 4:
                 raise ValueError("at most 4 drive channels per species")
         self.obs_channels_pred, self.obs_channels_prey = 4 + len(drive_lists[0]), 4 + len(drive_lists[1])
-        self._alloc_buffers(prey_capacity)
+        self._alloc_buffers(prey_capacity, pred_capacity)
         NG = self.grass_capacity
 
         c = _abi.PpgConfig()
@@ -145,8 +148,10 @@ class BatchedPredPreyGrass:
     def _abi_obs_dtype(self):
         return {torch.float64: 0, torch.float32: 1, torch.bfloat16: 2}[self.obs_dtype]
 
-    def _alloc_buffers(self, prey_capacity):
-        self.pred_capacity = PRED_CAPACITY
+    def _alloc_buffers(self, prey_capacity, pred_capacity=PRED_CAPACITY):
+        if pred_capacity not in PRED_CAPACITIES:
+            raise ValueError(f"pred_capacity must be one of {PRED_CAPACITIES}, got {pred_capacity!r}")
+        self.pred_capacity = int(pred_capacity)
         self.prey_capacity = int(prey_capacity)
         if self.n_grass > 255 and self.prey_capacity < 256:
             self.prey_capacity = 256   # up to 128 prey rows the kernels use 8-bit cell maps: at most 255 grass patches

@@ -11,26 +11,29 @@
         for (int q = 0; q < T; ++q) alive[q] &= ~((q == r) ? bit64(k) : 0ull);
     }
 
+    // The live predators of register PR selected by sel, in row order.  With two predator registers the caller runs register 0, then
+    // register 1: rows are in self.agents order across the register boundary.
+    template <int PR = 0>
     PPG_MEMBER void engage_predators(uint64_t sel = ~0ull) {
-        uint64_t m = alive[0] & sel;
+        uint64_t m = alive[PR] & sel;
         while (m) {
             const int k = wv::ctz(m);
             m &= m - 1;
-            const double s_e = readlane_f64(e[0], k);
-            const uint32_t s_xy = wv::readlane(xy[0], k);
-            if (s_e <= 0.0) { starve(0, k, s_xy); continue; }
+            const double s_e = readlane_f64(e[PR], k);
+            const uint32_t s_xy = wv::readlane(xy[PR], k);
+            if (s_e <= 0.0) { starve(PR, k, s_xy); continue; }
             uint64_t pm[T];
             match(1, s_xy, pm);
             int total = 0;
 #pragma unroll
-            for (int q = 1; q < T; ++q) total += wv::popc(pm[q]);
+            for (int q = NP; q < T; ++q) total += wv::popc(pm[q]);
             if (total == 0) continue;  // reward_predator_step, BASE:341
             // first prey in agent_positions order == lowest id (ids are handed out in insertion order)
             // (GEN2: the creation number sits in the top bits of row_id, so the same comparison picks the first-inserted prey)
             int cr = 0, ck = 0;
             uint32_t best = 0xFFFFFFFFu;
 #pragma unroll
-            for (int q = 1; q < T; ++q) {
+            for (int q = NP; q < T; ++q) {
                 uint64_t mq = pm[q];
                 while (mq) {
                     const int kk = wv::ctz(mq);
@@ -41,22 +44,22 @@
             }
             double pe = 0.0;
 #pragma unroll
-            for (int q = 1; q < T; ++q)
+            for (int q = NP; q < T; ++q)
                 if (q == cr) pe = readlane_f64(e[q], ck);
             double ne = s_e + pe;                           // BASE:324 (E1: pe may be <= 0)
             if (GEN2) {  // RQ:598-606: capped gain times the transfer efficiency, then the predator's energy cap
                 const double raw = (C.cap_gain_prey < pe) ? C.cap_gain_prey : pe;
                 ne = s_e + raw * C.eff_transfer;
                 ne = (C.max_e_pred < ne) ? C.max_e_pred : ne;
-                if (ln == k) keep[0] &= ~(uint32_t)PPG_ROW_GRID_E0;
+                if (ln == k) keep[PR] &= ~(uint32_t)PPG_ROW_GRID_E0;
             }
-            e[0] = writelane_f64(e[0], k, ne);
-            if (ln == k) ev[0] |= EV_ATE;                   // BASE:319
-            grid_set(0, k, s_xy, ne, true);                 // BASE:325
+            e[PR] = writelane_f64(e[PR], k, ne);
+            if (ln == k) ev[PR] |= EV_ATE;                  // BASE:319
+            grid_set(PR, k, s_xy, ne, true);                // BASE:325
             obs_row(1, row_of(cr, ck), s_xy, pe);           // BASE:327 (before the prey is erased)
             n_alive[1] -= 1;
 #pragma unroll
-            for (int q = 1; q < T; ++q) {
+            for (int q = NP; q < T; ++q) {
                 alive[q] &= ~((q == cr) ? bit64(ck) : 0ull);
                 ev[q] |= (q == cr && ln == ck) ? (uint32_t)EV_CAUGHT : 0u;
             }
@@ -78,7 +81,7 @@
         uint64_t ong[T], stv[T];
         uint64_t anystv = 0;
 #pragma unroll
-        for (int r = 1; r < T; ++r) {
+        for (int r = NP; r < T; ++r) {
             const uint64_t mine = alive[r] & (sel == 0 ? ~0ull : (sel == 2 ? t2m[r] : ~t2m[r]));
             const uint32_t gm = ((mine >> ln) & 1ull) ? (uint32_t)chmap(3)[cell_of(xy[r])] : 0u;
             pidx[r] = gm ? (uint32_t)from_map(3, gm) : 0u;   // 0 = not standing on a patch
@@ -90,7 +93,7 @@
         if (!anystv && !cooc[1]) {
             // no mid-step observation needed and one prey per cell: all eaters at once (BASE:359-372)
 #pragma unroll
-            for (int r = 1; r < T; ++r) {
+            for (int r = NP; r < T; ++r) {
                 if ((ong[r] >> ln) & 1ull) {
                     e[r] = prey_after_eating(e[r], val[pidx[r]]);
                     if (GEN2) keep[r] &= ~(uint32_t)PPG_ROW_GRID_E0;
@@ -104,7 +107,7 @@
             return;
         }
 #pragma unroll
-        for (int r = 1; r < T; ++r) {
+        for (int r = NP; r < T; ++r) {
             uint64_t m = ong[r] | stv[r];
             while (m) {
                 const int k = wv::ctz(m);

@@ -2,7 +2,7 @@
 // not a header of its own): the load phase: every global load of a step issued up front (Pre / prefetch), env words, rows, LDS initialisation, the cooperative kernels' tables, the grass table.
     // ---- load ----------------------------------------------------------------------
     // Every global load that does not depend on another load is issued first, back to back, so the
-    // wave pays ONE memory round trip: env words, seed, the first two row registers (speculatively:
+    // wave pays ONE memory round trip: env words, seed, the predator registers and the first prey register (speculatively:
     // rows beyond n_rows are valid memory holding stale data and are masked out), the first 128 grass
     // patches and the observation descriptor table.
     struct Pre {
@@ -24,7 +24,7 @@
 #pragma unroll
         for (int r = 0; r < T; ++r) {
             p.xy[r] = 0xFFFFu; p.key[r] = 0; p.fl[r] = 0; p.id[r] = 0; p.a[r] = -1; p.e[r] = 0.0; p.cum[r] = 0.0;
-            if (r < 2 && want_rows) {
+            if (r < NP + 1 && want_rows) {
                 const size_t s = (size_t)b * P.S + slot_of(r, ln);
                 p.xy[r] = C.row_xy[s];
                 p.e[r] = C.row_e[s];
@@ -82,7 +82,7 @@
             uint32_t fl = 0;
             xy[r] = 0xFFFFu; id[r] = 0; key[r] = 0; e[r] = 0.0; act[r] = -1; ev[r] = 0; cum[r] = 0.0;
             if (valid) {
-                if (r < 2) {
+                if (r < NP + 1) {
                     xy[r] = p.xy[r]; e[r] = p.e[r]; id[r] = p.id[r]; key[r] = p.key[r];
                     fl = p.fl[r]; act[r] = p.a[r];
                     if (CARRY_CUM) cum[r] = p.cum[r];

@@ -21,7 +21,7 @@
     }
     // the value grid[type, pos] shows for this lane's row: its energy, or the birth value (RQ:760)
     PPG_MEMBER double shown(int r) const {
-        if (GEN2 && (keep[r] & PPG_ROW_GRID_E0)) return r ? C.e0_q : C.e0_p;
+        if (GEN2 && (keep[r] & PPG_ROW_GRID_E0)) return PPG_PREY(r) ? C.e0_q : C.e0_p;
         return e[r];
     }
     PPG_MEMBER bool shown_positive(int r) const {
@@ -35,10 +35,18 @@
             uint32_t w[4];
 #pragma unroll
             for (int r = 0; r < T; ++r) {
-                if ((r & 3) == 0)
-                    philox4x32_10((uint32_t)step, (uint32_t)ln + 64u * (uint32_t)(r >> 2), 0u, episode,
-                                  (uint32_t)seed, (uint32_t)(seed >> 32) ^ TAG_ACT, w);
-                act[r] = (int32_t)wv::mulhi(w[r & 3], (uint32_t)n_actions(r));
+                if constexpr (NP == 1) {
+                    if ((r & 3) == 0)
+                        philox4x32_10((uint32_t)step, (uint32_t)ln + 64u * (uint32_t)(r >> 2), 0u, episode,
+                                      (uint32_t)seed, (uint32_t)(seed >> 32) ^ TAG_ACT, w);
+                    act[r] = (int32_t)wv::mulhi(w[r & 3], (uint32_t)n_actions(r));
+                } else {   // the oracle's register numbering (rng_reg): both predator registers read the words of register 0
+                    const int g = rng_reg(r);
+                    if ((g & 3) == 0 && (r == 0 || rng_reg(r - 1) != g))
+                        philox4x32_10((uint32_t)step, (uint32_t)ln + 64u * (uint32_t)(g >> 2), 0u, episode,
+                                      (uint32_t)seed, (uint32_t)(seed >> 32) ^ TAG_ACT, w);
+                    act[r] = (int32_t)wv::mulhi(w[g & 3], (uint32_t)n_actions(r));
+                }
             }
         } else {
 #pragma unroll
@@ -59,9 +67,9 @@
     }
 
     // Explicit action order (a dict whose order differs from the previous observation dict): rows of
-    // `type` that act, as (register, lane) pairs in action order, through the LDS scratch.
+    // `type` that act, as (register, lane) pairs in action order, through the LDS scratch (predators first, 64 * NP entries).
     PPG_MEMBER int publish_order(int type, const uint64_t (&acted)[T]) {
-        uint16_t *ord = (uint16_t *)scr + (type ? 64 : 0);
+        uint16_t *ord = (uint16_t *)scr + (type ? 64 * NP : 0);
         int n = 0;
         wv::sync();
 #pragma unroll
@@ -74,9 +82,9 @@
         return n;
     }
     PPG_MEMBER void ordered_row(int type, int i, int &r, int &k) const {
-        const uint16_t *ord = (const uint16_t *)scr + (type ? 64 : 0);
+        const uint16_t *ord = (const uint16_t *)scr + (type ? 64 * NP : 0);
         const int row = (int)wv::first((uint32_t)ord[i]);
-        r = type ? 1 + (row >> 6) : 0;
+        r = PPG_REG_OF(type, row);
         k = row & 63;
     }
     // xy of row (r,k) where r may be a run-time (wave-uniform) register index.  The lane is read from every
@@ -131,7 +139,7 @@
 #pragma unroll
         for (int r = 0; r < T; ++r)
             if ((acted[r] >> ln) & 1ull) {
-                e[r] -= (r ? C.loss_q : C.loss_p);
+                e[r] -= (PPG_PREY(r) ? C.loss_q : C.loss_p);
                 if (GEN2) keep[r] &= ~(uint32_t)PPG_ROW_GRID_E0;  // RQ:489: the grid now shows the real energy
             }
 
@@ -257,9 +265,10 @@
         uint64_t moved[T], sp[T];
         const bool costly = GEN2 && C.move_factor != 0.0;
         // distance * factor per squared displacement (RQ:310-312), once per wavefront in the LDS scratch instead of a chain of selects
-        // per row register.  BEHIND the explicit-order path's row lists (publish_order: predators at bytes 0..127, prey at
-        // 128..128 + 2 * cap_prey <= 640): bytes 640..895 of a scratch that is at least 1024 bytes in every layout (ppg_host.h).
-        double *cost = (double *)scr + 80;
+        // per row register.  BEHIND the explicit-order path's row lists (publish_order: predators at bytes 0..128 NP - 1, prey at
+        // 128 NP..128 NP + 2 * cap_prey <= 640 / 768): bytes 640..895 (NP 2: 768..1023) of a scratch that is at least 1024 bytes in
+        // every layout (ppg_host.h).
+        double *cost = (double *)scr + (NP == 1 ? 80 : 96);
         if (costly) {
             if (ln < 32) cost[ln] = ln < 19 ? move_distance(ln) * C.move_factor : 0.0;   // (rows not in use index anything below 32)
             wv::sync();

@@ -59,7 +59,7 @@
     PPG_MEMBER void reproduce() {
         uint64_t cand[T];
 #pragma unroll
-        for (int r = 0; r < T; ++r) cand[r] = alive[r] & wv::ballot(e[r] >= (r ? C.thr_q : C.thr_p));
+        for (int r = 0; r < T; ++r) cand[r] = alive[r] & wv::ballot(e[r] >= (PPG_PREY(r) ? C.thr_q : C.thr_p));
 #pragma unroll
         for (int r = 0; r < T; ++r) {
             const int type = type_of(r);
@@ -94,7 +94,7 @@
                 }
                 next_id[type] += 1;                        // BASE:397/426
                 const int j = n_rows[type]++;              // appended to self.agents, BASE:398/427
-                const int cr = type ? 1 + (j >> 6) : 0, ck = j & 63;
+                const int cr = PPG_REG_OF(type, j), ck = j & 63;
                 const uint32_t ckey = lexkey((uint32_t)cid);
 #pragma unroll
                 for (int q = 0; q < T; ++q) {
@@ -188,7 +188,7 @@
         const int seq = next_id[0] + next_id2[0] + next_id[1] + next_id2[1];  // agents created so far this episode
         if (nty) next_id2[SP] += 1; else next_id[SP] += 1;    // RQ:728
         const int j = n_rows[SP]++;                           // appended to self.agents, RQ:729
-        const int cr = SP ? 1 + (j >> 6) : 0, ck = j & 63;
+        const int cr = PPG_REG_OF(SP, j), ck = j & 63;
         const uint32_t cidw = ((uint32_t)seq << 17) | ((uint32_t)nty << 16) | (uint32_t)cur;
         const uint32_t ckey = (nty ? KEY_TYPE2 : 0u) + lexkey((uint32_t)cur);
         const double e0 = SP ? C.e0_q : C.e0_p;
@@ -226,7 +226,7 @@
 #pragma unroll
         for (int r = 0; r < T; ++r) {
             elig[r] = alive[r] & wv::ballot(step - lr[r] >= C.cooldown);                 // RQ:697
-            cand[r] = elig[r] & wv::ballot(e[r] >= (r ? C.thr_q : C.thr_p));             // RQ:704/789
+            cand[r] = elig[r] & wv::ballot(e[r] >= (PPG_PREY(r) ? C.thr_q : C.thr_p));    // RQ:704/789
         }
         // Every eligible agent draws once (chance gate); only those with enough energy matter afterwards.  Publish
         // the candidates in self.agents order, each with the number of eligible agents in front of it.
@@ -258,8 +258,8 @@
             if (uniform(d1) > (species ? C.chance_q : C.chance_p)) continue;             // RQ:701-702
             const double u2 = uniform(d1 + 1);                                          // RQ:708/793
             n_second += 1;
-            if (species) spawn2<1>(1 + (row >> 6), row & 63, u2 < C.mut_q);
-            else spawn2<0>(0, row & 63, u2 < C.mut_p);
+            if (species) spawn2<1>(NP + (row >> 6), row & 63, u2 < C.mut_q);
+            else spawn2<0>(NP == 1 ? 0 : (row >> 6), row & 63, u2 < C.mut_p);
         }
         draws = base + n_second;
     }

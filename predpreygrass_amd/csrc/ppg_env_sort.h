@@ -17,7 +17,12 @@
                 for (int r = T - 1; r >= 0; --r) {
                     if (type_of(r) != type) continue;
                     uint32_t prev = wv::shfl_up1(key[r]);
-                    if (r >= 2) {
+                    if constexpr (NP == 1) {
+                        if (r >= 2) {
+                            uint32_t carry = wv::readlane(key[r - 1], 63);
+                            if (ln == 0) prev = carry;
+                        }
+                    } else if (r >= 1 && type_of(r - 1) == type) {   // (the previous register holds rows of the same type)
                         uint32_t carry = wv::readlane(key[r - 1], 63);
                         if (ln == 0) prev = carry;
                     }

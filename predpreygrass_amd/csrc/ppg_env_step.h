@@ -49,14 +49,14 @@
                         rew = t2 ? C.r2_caught[1] : C.r2_caught[0]; c += rew;           // RQ:616-618
                     } else {
                         if (v & EV_ATE) {
-                            rew = r ? (t2 ? C.r2_eat[1] : C.r2_eat[0]) : (t2 ? C.r2_catch[1] : C.r2_catch[0]);
+                            rew = PPG_PREY(r) ? (t2 ? C.r2_eat[1] : C.r2_eat[0]) : (t2 ? C.r2_catch[1] : C.r2_catch[0]);
                             c += rew; c += rew;                                          // RQ:596+643 / 663+691
                         } else {
-                            rew = r ? (t2 ? C.r2_qstep[1] : C.r2_qstep[0]) : (t2 ? C.r2_pstep[1] : C.r2_pstep[0]);
+                            rew = PPG_PREY(r) ? (t2 ? C.r2_qstep[1] : C.r2_qstep[0]) : (t2 ? C.r2_pstep[1] : C.r2_pstep[0]);
                             c += rew;                                                    // RQ:643 / 691
                         }
                         if (v & EV_PARENT) {                                             // RQ:719-721 / 767-769 overwrite
-                            rew = r ? (t2 ? C.r2_repro_q[1] : C.r2_repro_q[0]) : (t2 ? C.r2_repro_p[1] : C.r2_repro_p[0]);
+                            rew = PPG_PREY(r) ? (t2 ? C.r2_repro_q[1] : C.r2_repro_q[0]) : (t2 ? C.r2_repro_p[1] : C.r2_repro_p[0]);
                             c += rew;
                         }
                     }
@@ -66,23 +66,23 @@
                     const double before = C.row_e[(size_t)b * P.S + (keep[r] >> 8)];
                     rew = (v & EV_CAUGHT) ? (0.0 - before) : (e[r] - before);
                     if (C.reward_mode == 2 && !(v & (EV_STARVED | EV_CAUGHT)))
-                        rew = rew + ((v & EV_PARENT) ? (r ? C.r_repro_q : C.r_repro_p) : 0.0);
+                        rew = rew + ((v & EV_PARENT) ? (PPG_PREY(r) ? C.r_repro_q : C.r_repro_p) : 0.0);
                     c += rew;
                 } else if (v & EV_STARVED) {
                     rew = 0.0;
                 } else if (v & EV_CAUGHT) {
                     rew = C.r_caught; c += rew;
                 } else {
-                    if (v & EV_ATE) { rew = r ? C.r_eat : C.r_catch; c += rew; c += rew; }
-                    else { rew = r ? C.r_qstep : C.r_pstep; c += rew; }
+                    if (v & EV_ATE) { rew = PPG_PREY(r) ? C.r_eat : C.r_catch; c += rew; c += rew; }
+                    else { rew = PPG_PREY(r) ? C.r_qstep : C.r_pstep; c += rew; }
                     if (KICK) {
-                        const double kb = r ? C.kick_q : C.kick_p;
+                        const double kb = PPG_PREY(r) ? C.kick_q : C.kick_p;
                         const uint32_t n_before = (v >> 8) & 15u, n_after = (v >> 12) & 15u;
                         for (uint32_t i = 0; i < n_before; ++i) { rew = rew + kb; c = c + kb; }   // KICK:446-447
-                        if (v & EV_PARENT) { rew = r ? C.r_repro_q : C.r_repro_p; c += rew; }       // BASE:409 overwrites
+                        if (v & EV_PARENT) { rew = PPG_PREY(r) ? C.r_repro_q : C.r_repro_p; c += rew; }       // BASE:409 overwrites
                         for (uint32_t i = 0; i < n_after; ++i) { rew = rew + kb; c = c + kb; }
                     } else if (v & EV_PARENT) {
-                        rew = r ? C.r_repro_q : C.r_repro_p; c += rew;
+                        rew = PPG_PREY(r) ? C.r_repro_q : C.r_repro_p; c += rew;
                     }
                 }
                 if (v & (EV_STARVED | EV_CAUGHT)) fl |= PPG_ROW_DIED;
@@ -214,22 +214,22 @@
 #pragma unroll
         for (int r = 0; r < T; ++r) {
             const int i = row_of(r, ln);
-            const int cnt = r ? Q0 : P0;
+            const int cnt = PPG_PREY(r) ? Q0 : P0;
             const bool valid = i < cnt;
             xy[r] = 0xFFFFu; id[r] = 0; key[r] = 0; e[r] = 0.0; act[r] = -1; ev[r] = 0; keep[r] = 0;
             if (valid) {
-                const uint32_t c = ent[(r ? P0 : 0) + i];
+                const uint32_t c = ent[(PPG_PREY(r) ? P0 : 0) + i];
                 const uint32_t cx = wv::mulhi(c, C.g_magic);
                 xy[r] = (cx << 8) | (c - cx * (uint32_t)P.G);
                 id[r] = i;
                 key[r] = lexkey((uint32_t)i);
                 if (GEN2) {  // RQ:125-133: type 1 first, then type 2; creation number = position in self.agents
-                    const int n1 = r ? C.ninit2[2] : C.ninit2[0];
-                    const int t2 = i >= n1, idx = t2 ? i - n1 : i, seq = r ? P0 + i : i;
+                    const int n1 = PPG_PREY(r) ? C.ninit2[2] : C.ninit2[0];
+                    const int t2 = i >= n1, idx = t2 ? i - n1 : i, seq = PPG_PREY(r) ? P0 + i : i;
                     id[r] = (int32_t)(((uint32_t)seq << 17) | ((uint32_t)t2 << 16) | (uint32_t)idx);
                     key[r] = (t2 ? KEY_TYPE2 : 0u) + lexkey((uint32_t)idx);
                 }
-                e[r] = r ? C.e0_q : C.e0_p;
+                e[r] = PPG_PREY(r) ? C.e0_q : C.e0_p;
             }
             rows[r] = wv::ballot(valid);
             alive[r] = rows[r];
@@ -324,6 +324,7 @@
         PPG_STAMP(7);
         if (!GEN2 || list_is_row_order) {
             engage_predators();                    // BASE:302-346 (+ starvation BASE:284-301)
+            if constexpr (NP > 1) engage_predators<NP - 1>();   // (rows 64..127)
             wv::sync();
             PPG_STAMP(8);
             engage_prey();                         // BASE:347-380
@@ -331,11 +332,13 @@
         } else {
             // RQ:225-233 walks the sorted self.agents: type_1_predator*, type_1_prey*, type_2_predator*, type_2_prey*
             engage_predators(~t2m[0]);
+            if constexpr (NP > 1) engage_predators<NP - 1>(~t2m[NP - 1]);
             wv::sync();
             engage_prey(1);
             wv::sync();
             PPG_STAMP(8);
             engage_predators(t2m[0]);
+            if constexpr (NP > 1) engage_predators<NP - 1>(t2m[NP - 1]);
             wv::sync();
             engage_prey(2);
             wv::sync();

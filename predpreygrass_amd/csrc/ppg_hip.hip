@@ -10,7 +10,7 @@
 
 // The kernels are compiled in separate translation units (ppg_kernels.hip, one per generation and prey-register
 // count) so that the build runs in parallel; this unit holds the host side and only declares them.
-// kernel name: ppg_<mode>_q<prey registers>[g]   (g = generic observation geometry, descriptors in LDS);
+// kernel name: ppg_<mode>_[p2]q<prey registers>[g]   (g = generic observation geometry, descriptors in LDS; p2 = 128 predator rows);
 // ppg2_* = second generation (two agent types, stochastic reproduction)
 #define PPG_K(name, NQ, MODE, FAST) PPG_KERNEL(name, (NQ <= 2 ? 4 : 2))(const ppg::KParams P);
 #define PPG_K2(name, NQ, MODE, FAST) PPG_KERNEL(name, (NQ <= 2 ? 4 : 2))(const ppg::KParams P);
@@ -25,6 +25,8 @@
 #define PPG_KCM(name, NQ, GEN2) PPG_KERNEL_NW(name, 4, 4)(const ppg::KParams P);
 #define PPG_KCH(name, NQ) PPG_KERNEL_NW(name, 8, 4)(const ppg::KParams P);
 #define PPG_KCR(name, NQ, GEN2, NW) PPG_KERNEL_NW(name, 4, NW)(const ppg::KParams P);
+#define PPG_KP(name, NQ, MODE) PPG_KERNEL(name, (NQ <= 2 ? 4 : 2))(const ppg::KParams P);
+#define PPG_KP2(name, NQ, MODE) PPG_KERNEL(name, (NQ <= 2 ? 4 : 2))(const ppg::KParams P);
 #include "ppg_kernel_list.h"
 
 PPG_DEFINE_KERNELSC(1)
@@ -47,6 +49,10 @@ PPG_DEFINE_KERNELSW(4)
 PPG_DEFINE_KERNELSW2(1)
 PPG_DEFINE_KERNELSW2(2)
 PPG_DEFINE_KERNELSW2(4)
+PPG_DEFINE_KERNELSP(2)
+PPG_DEFINE_KERNELSP(4)
+PPG_DEFINE_KERNELSP2(2)
+PPG_DEFINE_KERNELSP2(4)
 
 typedef void (*ppg_kernel_fn)(const ppg::KParams);
 
@@ -91,6 +97,19 @@ static ppg_kernel_fn pick_kernel(int nq, int mode, bool fast) {
          {ppg_step_q4, ppg_reset_q4, ppg_observe_q4, ppg_grid_q4, ppg_step_ord_q4, ppg_rollout_q4, ppg_step_kick_q4, ppg_step_ord_kick_q4}},
     };
     return table[fast ? 1 : 0][nq == 1 ? 0 : nq == 2 ? 1 : 2][mode];
+}
+
+// 128 predator rows (ppg_kernel_list.h: PPG_DEFINE_KERNELSP / SP2): one wave per env, generic observation geometry, nq 2 or 4
+static ppg_kernel_fn pick_kernel_p2(bool gen2, int nq, int mode) {
+    static const ppg_kernel_fn base[2][ppg::N_MODES] = {
+        {ppg_step_p2q2g, ppg_reset_p2q2g, ppg_observe_p2q2g, ppg_grid_p2q2g, ppg_step_ord_p2q2g, ppg_rollout_p2q2g, ppg_step_kick_p2q2g,
+         ppg_step_ord_kick_p2q2g},
+        {ppg_step_p2q4g, ppg_reset_p2q4g, ppg_observe_p2q4g, ppg_grid_p2q4g, ppg_step_ord_p2q4g, ppg_rollout_p2q4g, ppg_step_kick_p2q4g,
+         ppg_step_ord_kick_p2q4g}};
+    static const ppg_kernel_fn second[2][5] = {
+        {ppg2_step_p2q2g, ppg2_reset_p2q2g, ppg2_observe_p2q2g, ppg2_grid_p2q2g, ppg2_step_ord_p2q2g},
+        {ppg2_step_p2q4g, ppg2_reset_p2q4g, ppg2_observe_p2q4g, ppg2_grid_p2q4g, ppg2_step_ord_p2q4g}};
+    return gen2 ? second[nq == 2 ? 0 : 1][mode] : base[nq == 2 ? 0 : 1][mode];
 }
 
 #define PPG_HIP_TRY(h, call)                                                                   \
@@ -237,6 +256,11 @@ static int backend_launch(ppg_handle *h, int mode, const ppg::KParams &P, void *
     if (h->drive && mode > ppg::MODE_STEP_ORDERED) return ppg_fail(h, PPG_EINVAL, "mode %d is not available for the drive-conditioned variant", mode);
     ppg_kernel_fn fn = h->drive ? pick_kernel_drive(h->nq, mode) : !h->gen2 ? pick_kernel(h->nq, mode, fast)
                        : h->cfg2.walls ? pick_kernel_walls(h->nq, mode) : pick_kernel_gen2(h->nq, mode, fast);
+    if (P.cap_pred > 64) {   // (ppg_validate_and_layout admits 128 predator rows for these forms only; ppg_wave_plan keeps them one-wave)
+        if (h->drive || (h->gen2 && h->cfg2.walls) || h->nq < 2 || P.coop_e > 0 || h->plan.nw != 1)
+            return ppg_fail(h, PPG_EINVAL, "no kernel for 128 predator rows with this configuration");
+        fn = pick_kernel_p2(h->gen2 != 0, h->nq, mode);
+    }
     unsigned block = 64, grid = (unsigned)h->batch;
     const ppg_wave_plan_t wp = h->plan;
     if ((mode == ppg::MODE_STEP || mode == ppg::MODE_ROLLOUT) && P.coop_e > 0) {   // cooperative kernels: coop_e envs per workgroup of wp.nw wavefronts

@@ -119,7 +119,14 @@ static int ppg_validate_and_layout(ppg_handle *h) {
     if (c.grid_size < 2 || c.grid_size > 88) return ppg_fail(h, PPG_EINVAL, "grid_size %d outside 2..88", c.grid_size);
     if (c.predator_obs_range < 1 || c.predator_obs_range > 15 || c.prey_obs_range < 1 || c.prey_obs_range > 15)
         return ppg_fail(h, PPG_EINVAL, "obs ranges must be in 1..15");
-    if (c.pred_capacity != 64) return ppg_fail(h, PPG_EINVAL, "pred_capacity must be 64");
+    if (c.pred_capacity != 64 && c.pred_capacity != 128) return ppg_fail(h, PPG_EINVAL, "pred_capacity must be 64 or 128");
+    if (c.pred_capacity == 128) {   // two predator row registers (Env's NP): one-wave kernels of the base family / second generation
+        if (c.prey_capacity != 128 && c.prey_capacity != 256)
+            return ppg_fail(h, PPG_EINVAL, "pred_capacity 128 needs prey_capacity 128 or 256");
+        if (h->gen2 && h->cfg2.walls) return ppg_fail(h, PPG_EINVAL, "pred_capacity 128 is not available for the walls variant");
+        if (!h->gen2 && (c.n_drive[0] > 0 || c.n_drive[1] > 0))
+            return ppg_fail(h, PPG_EINVAL, "pred_capacity 128 is not available for the drive-conditioned variant");
+    }
     if (c.prey_capacity != 64 && c.prey_capacity != 128 && c.prey_capacity != 256)
         return ppg_fail(h, PPG_EINVAL, "prey_capacity must be 64, 128 or 256");
     if (c.n_grass < 0 || c.grass_capacity < c.n_grass || c.grass_capacity % 64 != 0 || c.grass_capacity > 4096)
@@ -205,7 +212,8 @@ static int ppg_validate_and_layout(ppg_handle *h) {
     // the descriptor table lives in LDS only for the kernels that read it from there: the FASTOBS kernels (base family / second
     // generation with <= 2 predator and <= 3 prey chunks: the same rule as the backends' kernel selection) keep it in registers.
     // (64x64 grid, 7x7 windows: 24080 -> 22032 bytes per env = 7 instead of 6 envs per CU.)
-    const bool lut_in_registers = P.nch_p <= 2 && P.nch_q <= 3 && !drive && !(h->gen2 && h->cfg2.walls)
+    // (128 predator rows: the generic kernels only)
+    const bool lut_in_registers = P.nch_p <= 2 && P.nch_q <= 3 && !drive && !(h->gen2 && h->cfg2.walls) && P.cap_pred == 64
 #ifdef PPG_WAVE_EMU   // (tests: exercise the LDS-descriptor observation path on configurations that would keep it in registers)
                                   && !getenv("PPG_EMU_FORCE_GENERIC_OBS")
 #endif
@@ -438,6 +446,7 @@ static ppg_wave_plan_t ppg_wave_plan(const ppg_handle *h) {
     const int in_flight = h->envs_in_flight > 0 ? h->envs_in_flight : h->batch;
     const bool walls = h->gen2 && h->cfg2.walls;
     ppg_wave_plan_t p = {1, 0, 0};
+    if (h->base.cap_pred > 64) return p;   // 128 predator rows: one-wave kernels only (ppg_set_wave_plan refuses any other plan)
     if (h->forced.nw > 0) {
         p = h->forced;
         if (walls || h->drive) {   // (pair and four-wave kernels, helpers always stay; walls: the four-wave cooperative kernel)
@@ -819,6 +828,8 @@ int ppg_set_envs_in_flight(ppg_handle *h, int32_t envs_in_flight) {
 int ppg_set_wave_plan(ppg_handle *h, int32_t waves, int32_t helper_min_rows, int32_t coop_envs) {
     if (!h) return PPG_EINVAL;
     if (waves < 0 || helper_min_rows < 0 || coop_envs < 0) return ppg_fail(h, PPG_EINVAL, "negative wave plan");
+    if (h->base.cap_pred > 64 && (waves > 1 || coop_envs > 0))
+        return ppg_fail(h, PPG_EINVAL, "a handle with 128 predator rows has one-wave kernels only (waves %d, coop_envs %d)", waves, coop_envs);
     h->forced = {waves, helper_min_rows, coop_envs};
     h->plan = ppg_wave_plan(h);
     return PPG_OK;
@@ -864,6 +875,10 @@ const char *ppg_step_kernel_name(ppg_handle *h) {
     char fam[8];
     if (wp.nw == 8 && h->gen2 && !walls) snprintf(fam, sizeof fam, "w28");
     else snprintf(fam, sizeof fam, "%s%s", wp.nw == 8 ? "w8" : waves, family);
+    if (h->base.cap_pred > 64) {   // ppg_step_[kick_]p2q<NQ>g / ppg2_step_p2q<NQ>g
+        snprintf(h->kernel_name, sizeof h->kernel_name, "ppg%s_step_%sp2q%dg", family, h->cfg.kickback ? "kick_" : "", h->nq);
+        return h->kernel_name;
+    }
     snprintf(h->kernel_name, sizeof h->kernel_name, "ppg%s_step_%sq%d%s", fam, h->cfg.kickback && wp.nw == 1 ? "kick_" : "", h->nq,
              (fast || walls || h->drive) ? "" : "g");
     return h->kernel_name;

@@ -1,7 +1,8 @@
 // ppg_kernel.h -- the PredPreyGrass transition as hand-written HIP for gfx950 (MI355X).
 //
 // ONE 64-LANE WAVEFRONT STEPS ONE ENVIRONMENT.  Lane l holds agent row l of each row
-// register (register 0: predator rows 0..63; register 1+q: prey rows 64q..64q+63), so the
+// register (register 0: predator rows 0..63 -- and register 1 rows 64..127 in the kernels of
+// 128 predator rows, Env's NP; then prey rows 64q..64q+63), so the
 // whole agent table lives in VGPRs and the per-agent flags live in 64-bit SGPR masks.
 // Order-dependent phases of the reference (movement in action order, engagement in
 // self.agents order, spawning) run as wave-uniform scalar loops over mask bits that read
@@ -299,10 +300,17 @@ PPG_DEVICE void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3
 // LDS decides the occupancy (round 6: 64x64 grids 24.1 -> 18.1 KB per env = four instead of three workgroups per CU) channel 0 has
 // NO map and is computed from the window position (KParams::ch0_map 0; the extra arithmetic per element costs the float32 rows of
 // the second generation 11 %, so the small grids keep their fourth map).
-template <int NQ, bool ORDERED, bool FASTOBS, bool FUSED, bool KICK, bool GEN2, bool WALLS, bool DRIVE, int NW, class KP, class KC, bool COOP = false, bool CH0MAP = true>
+// NP: predator row registers -- 1 (64 predator rows) everywhere except the one-wave kernels of 128 predator rows (ppg_*_p2q<NQ>g,
+// ppg2_*_p2q<NQ>g: base family and second generation without walls, generic observation geometry).  Registers 0..NP-1 hold the
+// predators, NP..T-1 the prey.
+template <int NQ, bool ORDERED, bool FASTOBS, bool FUSED, bool KICK, bool GEN2, bool WALLS, bool DRIVE, int NW, class KP, class KC, bool COOP = false, bool CH0MAP = true, int NP = 1>
 struct Env {
-    static constexpr int T = 1 + NQ;  // row registers: 0 = predators, 1.. = prey
+    static constexpr int T = NP + NQ;  // row registers: 0..NP-1 = predators, NP.. = prey
     static constexpr bool MAP8 = NQ <= 2;
+    static_assert(NP == 1 || (NP == 2 && NW == 1 && !COOP && !FASTOBS && !WALLS && !DRIVE && NQ >= 2),
+                  "128 predator rows: one-wave kernels of the base family / second generation without walls, generic observations");
+    // 8-bit cell maps: the predator section of the value table is 1..128 (SEC_Q below), so predator rows + 1 fit a byte with bit 7
+    // free only for 64 rows -- the cooperative kernels' borrowed bit 7 (fallback_spawn) needs NP == 1, which the assert above gives
     // Helper wavefronts that leave light envs to wave 0 (KParams::helper_min_rows) need BOTH observation paths in one kernel.  The
     // walls and drive variants' observation code is large: with two copies of it their kernels ran 10-15 % slower, so their helpers
     // always stay.
@@ -390,16 +398,31 @@ struct Env {
           scr((uint64_t *)(lds + p.off_scr)), lut((uint32_t *)(lds + p.off_lut)), wallw((uint32_t *)(lds + c.off_wall)) {}
 
     // ---- index helpers -------------------------------------------------------------
-    static PPG_MEMBER int type_of(int r) { return r ? 1 : 0; }
-    static PPG_MEMBER int row_of(int r, int k) { return r ? (r - 1) * 64 + k : k; }  // row within its type
-    PPG_MEMBER int slot_of(int r, int k) const { return r ? P.cap_pred + (r - 1) * 64 + k : k; }  // row in [0,S)
+    // (NP == 1 ? old : new): the front end folds the test, so the kernels of one predator register compile exactly as before NP
+    // existed -- `r >= 1` instead of `r` is the same value but not the same code once LLVM has optimised the rolled loops)
+    static PPG_MEMBER int type_of(int r) { return NP == 1 ? (r ? 1 : 0) : (r >= NP ? 1 : 0); }
+    static PPG_MEMBER int row_of(int r, int k) { return NP == 1 ? (r ? (r - 1) * 64 + k : k) : (r >= NP ? (r - NP) * 64 + k : r * 64 + k); }  // row within its type
+    PPG_MEMBER int slot_of(int r, int k) const {   // row in [0,S)
+        return NP == 1 ? (r ? P.cap_pred + (r - 1) * 64 + k : k) : (r >= NP ? P.cap_pred + (r - NP) * 64 + k : r * 64 + k);
+    }
+    // the register whose Philox words give a row its random action: the oracle's numbering (predators 0, prey 1 + row / 64), so
+    // predator rows 64..127 draw the words of rows 0..63 (oracle/ppg_oracle.c: ppo_random_action)
+    static PPG_MEMBER int rng_reg(int r) { return r >= NP ? r - NP + 1 : 0; }
+    // "register r holds prey" as a selector of species constants: the register index itself when there is one predator register
+    // (see type_of); a macro, not a function, so that the selection compiles as it did before
+#define PPG_PREY(r) (NP == 1 ? (r) : (int)((r) >= NP))
+    // the register of row `row` of type `type`, same idea (with one predator register every predator row is in register 0)
+#define PPG_REG_OF(type, row) ((type) ? NP + ((row) >> 6) : (NP == 1 ? 0 : ((row) >> 6)))
     // Index of an entity's energy in the LDS value table.  16-bit maps: [0] = 0.0, then all row slots, then the grass patches.
     // MAP8: one section per channel, each led by a zero entry so that "map entry + section base" needs no test for an empty cell:
-    // [0] = 0.0 | predators 1..64 || [129] = 0.0 | prey 130..257 || [258] = 0.0 | grass 259..513  (section base = 129 * (channel - 1)).
+    // [0] = 0.0 | predators 1..64 (NP 2: 1..128) || [129] = 0.0 | prey 130..257 || [258] = 0.0 | grass 259..513  (section base = 129 * (channel - 1)).
     // The cooperative kernels pack the sections (LDS decides how many envs a CU holds): [0] = 0.0 | predators 1..64 | [65] = 1.0 (the
     // "outside the grid" value of channel 0's halo, ch0_map 1) || [66] = 0.0 | prey 67..194 || [195] = 0.0 | grass 196...
     static constexpr int SEC_Q = COOP ? 66 : 129, SEC_G = SEC_Q + 129;
-    PPG_MEMBER int validx(int r, int k) const { return MAP8 ? (r ? SEC_Q + 1 + row_of(r, k) : 1 + k) : 1 + slot_of(r, k); }
+    PPG_MEMBER int validx(int r, int k) const {
+        return NP == 1 ? (MAP8 ? (r ? SEC_Q + 1 + row_of(r, k) : 1 + k) : 1 + slot_of(r, k))
+                       : (MAP8 ? (r >= NP ? SEC_Q + 1 + row_of(r, k) : 1 + row_of(r, k)) : 1 + slot_of(r, k));
+    }
     PPG_MEMBER int validx_row(int type, int row) const { return MAP8 ? (type ? SEC_Q + 1 + row : 1 + row) : 1 + (type ? P.cap_pred + row : row); }
     PPG_MEMBER int grass_validx(int p) const { return MAP8 ? SEC_G + 1 + p : 1 + P.S + p; }
     PPG_MEMBER int cell_of(uint32_t s_xy) const {
@@ -536,8 +559,16 @@ struct Env {
 #include "ppg_env_step.h"       // rewards + stores, device reset, step_body, run_*
 };
 
-template <int NQ, int MODE, bool FASTOBS, bool GEN2 = false, bool WALLS = false, bool DRIVE = false, int NW = 1>
+template <int NQ, int MODE, bool FASTOBS, bool GEN2 = false, bool WALLS = false, bool DRIVE = false, int NW = 1, int NP = 1>
 PPG_DEVICE void env_main(const KParams &P, unsigned char *lds) {
+#ifdef PPG_WAVE_EMU
+    // (the wave emulator has one entry per family and prey-register count: a handle with 128 predator rows reaches the kernels of
+    // two predator registers from here -- exactly the forms the library has; on the GPU they are kernel symbols of their own)
+    if constexpr (NP == 1 && NW == 1 && !WALLS && !DRIVE && NQ >= 2 &&
+                  (!GEN2 || MODE <= MODE_STEP_ORDERED) && MODE != MODE_VIS) {
+        if (P.cap_pred > 64) { env_main<NQ, MODE, false, GEN2, false, false, 1, 2>(P, lds); return; }
+    }
+#endif
     int b = PPG_BLOCK_INDEX();
     if (b >= P.batch) return;
     {   // scheduling only: heavy envs first, so that consecutive workgroups (which land on different CUs) spread the load
@@ -562,7 +593,8 @@ PPG_DEVICE void env_main(const KParams &P, unsigned char *lds) {
             PPG_LAUNDER_S(bb);
             PPG_LAUNDER_V(lane);
             PPG_LAUNDER_V(l);
-            Env<NQ, false, FASTOBS, true, false, false, false, false, 1, const PPG_CONSTANT_AS KParams, const PPG_CONSTANT_AS KParams> env(*Pc, *Pc, bb, l, lane);
+            Env<NQ, false, FASTOBS, true, false, false, false, false, 1, const PPG_CONSTANT_AS KParams, const PPG_CONSTANT_AS KParams, false, true, NP>
+                env(*Pc, *Pc, bb, l, lane);
             env.run_step(it);
             wv::sync();
         }
@@ -570,7 +602,7 @@ PPG_DEVICE void env_main(const KParams &P, unsigned char *lds) {
     }
     const PPG_CONSTANT_AS KParams *Pcold = PPG_KERNARG_PTR(KParams, P);  // KParams is the kernel's only argument
     Env<NQ, MODE == MODE_STEP_ORDERED || MODE == MODE_STEP_ORDERED_KICK, FASTOBS, false,
-        MODE == MODE_STEP_KICK || MODE == MODE_STEP_ORDERED_KICK, GEN2, WALLS, DRIVE, NW, const KParams, const PPG_CONSTANT_AS KParams>
+        MODE == MODE_STEP_KICK || MODE == MODE_STEP_ORDERED_KICK, GEN2, WALLS, DRIVE, NW, const KParams, const PPG_CONSTANT_AS KParams, false, true, NP>
         env(P, *Pcold, b, lds, wv::lane());
     if (NW > 1) {
         const int w = wv::wave_index();

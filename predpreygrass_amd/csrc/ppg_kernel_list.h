@@ -84,3 +84,22 @@
     PPG_K2(ppg2_observe_q##NQ##g, NQ, ppg::MODE_OBSERVE, false)       \
     PPG_K2(ppg2_grid_q##NQ##g, NQ, ppg::MODE_EXPORT_GRID, false)      \
     PPG_K2(ppg2_step_ord_q##NQ##g, NQ, ppg::MODE_STEP_ORDERED, false)
+
+// 128 predator rows (two predator row registers, Env's NP): one-wave kernels with the generic observation geometry, prey capacity 128 or
+// 256 (NQ 2 / 4) -- ppg_<mode>_p2q<NQ>g of the base family, ppg2_<mode>_p2q<NQ>g of the second generation without walls
+#define PPG_DEFINE_KERNELSP(NQ)                                       \
+    PPG_KP(ppg_step_p2q##NQ##g, NQ, ppg::MODE_STEP)                   \
+    PPG_KP(ppg_reset_p2q##NQ##g, NQ, ppg::MODE_RESET)                 \
+    PPG_KP(ppg_observe_p2q##NQ##g, NQ, ppg::MODE_OBSERVE)             \
+    PPG_KP(ppg_grid_p2q##NQ##g, NQ, ppg::MODE_EXPORT_GRID)            \
+    PPG_KP(ppg_step_ord_p2q##NQ##g, NQ, ppg::MODE_STEP_ORDERED)       \
+    PPG_KP(ppg_rollout_p2q##NQ##g, NQ, ppg::MODE_ROLLOUT)             \
+    PPG_KP(ppg_step_kick_p2q##NQ##g, NQ, ppg::MODE_STEP_KICK)         \
+    PPG_KP(ppg_step_ord_kick_p2q##NQ##g, NQ, ppg::MODE_STEP_ORDERED_KICK)
+
+#define PPG_DEFINE_KERNELSP2(NQ)                                      \
+    PPG_KP2(ppg2_step_p2q##NQ##g, NQ, ppg::MODE_STEP)                 \
+    PPG_KP2(ppg2_reset_p2q##NQ##g, NQ, ppg::MODE_RESET)               \
+    PPG_KP2(ppg2_observe_p2q##NQ##g, NQ, ppg::MODE_OBSERVE)           \
+    PPG_KP2(ppg2_grid_p2q##NQ##g, NQ, ppg::MODE_EXPORT_GRID)          \
+    PPG_KP2(ppg2_step_ord_p2q##NQ##g, NQ, ppg::MODE_STEP_ORDERED)

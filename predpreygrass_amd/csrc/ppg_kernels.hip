@@ -1,7 +1,8 @@
 // ppg_kernels.hip -- one group of gfx950 kernels of libppg_hip.so per compilation:
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c -DPPG_TU_GEN=<1|2|3> -DPPG_TU_NQ=<1|2|4> ppg_kernels.hip
 // (1 = base family, 2 = second generation, 3 = second generation with walls, 4 = base family with drive channels, 5 = cooperative
-// step kernels of the base family; NQ = prey row registers).  Host code: ppg_hip.hip.
+// step kernels of the base family; NQ = prey row registers; units 1 and 2 with NQ 2 / 4 also hold the kernels of 128 predator rows).
+// Host code: ppg_hip.hip.
 #include <hip/hip_runtime.h>
 
 #include "ppg_kernel.h"
@@ -58,6 +59,14 @@
 #endif
 #define PPG_KC3(name, NQ)                                                                    \
     PPG_KERNEL_NW(name, PPG_WPE_COOP_WALLS, 4)(const ppg::KParams P) { PPG_DYNAMIC_LDS(lds); ppg::coop_walls_main<NQ>(P, lds); }
+// 128 predator rows (Env's NP = 2): one wave per env, generic observation geometry
+#ifndef PPG_WPE_P2
+#define PPG_WPE_P2 PPG_WPE
+#endif
+#define PPG_KP(name, NQ, MODE)                                                               \
+    PPG_KERNEL(name, (NQ <= 2 ? PPG_WPE_P2 : 2))(const ppg::KParams P) { PPG_DYNAMIC_LDS(lds); ppg::env_main<NQ, MODE, false, false, false, false, 1, 2>(P, lds); }
+#define PPG_KP2(name, NQ, MODE)                                                              \
+    PPG_KERNEL(name, (NQ <= 2 ? PPG_WPE_P2 : 2))(const ppg::KParams P) { PPG_DYNAMIC_LDS(lds); ppg::env_main<NQ, MODE, false, true, false, false, 1, 2>(P, lds); }
 #define PPG_KCR(name, NQ, GEN2, NW)                                                          \
     PPG_KERNEL_NW(name, PPG_WPE, NW)(const ppg::KParams P) { PPG_DYNAMIC_LDS(lds); ppg::coop_main_fused<NQ, GEN2, NW>(P, lds); }
 #include "ppg_kernel_list.h"
@@ -66,9 +75,15 @@
 #if PPG_TU_GEN == 1
 PPG_APPLY(PPG_DEFINE_KERNELS, PPG_TU_NQ)
 PPG_APPLY(PPG_DEFINE_KERNELSW, PPG_TU_NQ)
+#if PPG_TU_NQ >= 2
+PPG_APPLY(PPG_DEFINE_KERNELSP, PPG_TU_NQ)   // (128 predator rows need at least 128 prey rows)
+#endif
 #elif PPG_TU_GEN == 2
 PPG_APPLY(PPG_DEFINE_KERNELS2, PPG_TU_NQ)
 PPG_APPLY(PPG_DEFINE_KERNELSW2, PPG_TU_NQ)
+#if PPG_TU_NQ >= 2
+PPG_APPLY(PPG_DEFINE_KERNELSP2, PPG_TU_NQ)
+#endif
 #elif PPG_TU_GEN == 3
 PPG_APPLY(PPG_DEFINE_KERNELS3, PPG_TU_NQ)
 #elif PPG_TU_GEN == 5

@@ -1959,6 +1959,13 @@ int ppg_policy_act(ppg_policy *pred, ppg_policy *prey, ppg_handle *const *handle
     if (!any) return PPG_EINVAL;
     if (!handles || !actions || n < 1 || n > ppgpol::MAX_HANDLES || !handles[0]) return ppg_policy_fail(any, PPG_EINVAL, "bad handle list");
     if (flags & ~(PPG_POLICY_SAMPLE | PPG_POLICY_SEED_ON_DEVICE)) return ppg_policy_fail(any, PPG_EINVAL, "unknown policy flags 0x%x", flags);
+    for (int32_t k = 0; k < n; ++k)   // (the policy kernels read 64 predator rows per env)
+        if (handles[k] && handles[k]->base.cap_pred != 64) {
+            const int rc = ppg_policy_fail(any, PPG_EINVAL, "handle %d has %d predator rows; the policy kernels take handles with 64", k,
+                                           handles[k]->base.cap_pred);
+            memcpy(g_ppg_policy_error, any->err, sizeof g_ppg_policy_error);   // (ppg_policy_last_error(NULL))
+            return rc;
+        }
     if (pred && prey && pred->pipe && prey->pipe && pred->device == prey->device && pred->grid == prey->grid && ppg_fused_enabled()) {
         const int rc = ppg_policy_run_fused(pred, prey, handles, n, actions, flags, seed, logits_pred, logits_prey, stream);
         if (rc != 1) return rc;

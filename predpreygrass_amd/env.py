@@ -78,9 +78,20 @@ def _parse(name: str):
     return (PREDATOR if kind == "predator" else PREY), int(idx)
 
 
+def _pred_capacity_for(cfg, pred_capacity) -> int:
+    """Predator rows of a dict-class env: `pred_capacity` (64 or 128), else 64 -- more initial predators than that are refused with a
+    message that names the keyword (the drive-conditioned variant has 64 predator rows only: the library refuses it there)."""
+    if pred_capacity is not None:
+        return pred_capacity
+    n = int(cfg["n_initial_active_predator"])
+    if n > 64 and not cfg.get("enable_drive_channels", False):
+        raise ValueError(f"{n} initial predators exceed the default row capacity of 64: construct the env with pred_capacity=128")
+    return 64
+
+
 class PredPreyGrass(_MultiAgentEnvBase):
     def __init__(self, config=None, *, device=None, batched: BatchedPredPreyGrass | None = None, index: int = 0,
-                 prey_capacity: int | None = None, _library=None):
+                 prey_capacity: int | None = None, _library=None, pred_capacity: int | None = None):
         super().__init__()
         cfg = resolve_config(config)  # `config or config_env`, predpreygrass_rllib_env.py:20
         self.config = cfg
@@ -88,8 +99,8 @@ class PredPreyGrass(_MultiAgentEnvBase):
             setattr(self, k, v)
         if batched is None:
             need = max(128, (self.n_initial_active_prey + 63) // 64 * 64)
-            batched = BatchedPredPreyGrass(cfg, batch_size=1, device=device,
-                                           prey_capacity=prey_capacity or min(256, need), _library=_library)
+            batched = BatchedPredPreyGrass(cfg, batch_size=1, device=device, prey_capacity=prey_capacity or min(256, need),
+                                           _library=_library, pred_capacity=_pred_capacity_for(cfg, pred_capacity))
             index = 0
         self._b = batched
         self._i = int(index)
@@ -435,11 +446,12 @@ class VectorPredPreyGrass:
     is ignored for that call and the returned observations are those of the new episode, rewards 0)."""
 
     def __init__(self, config=None, num_envs=8, device=None, seed=0, auto_reset=False, prey_capacity=128,
-                 _library=None):
+                 _library=None, pred_capacity=None):
         self.num_envs = int(num_envs)
         self.auto_reset = bool(auto_reset)
         self.batch = BatchedPredPreyGrass(config, batch_size=self.num_envs, device=device, seed=seed,
-                                          prey_capacity=prey_capacity, _library=_library)
+                                          prey_capacity=prey_capacity, _library=_library,
+                                          pred_capacity=_pred_capacity_for(resolve_config(config), pred_capacity))
         self.envs = [PredPreyGrass(config, batched=self.batch, index=i) for i in range(self.num_envs)]
 
     def _collect_all(self, after_reset):

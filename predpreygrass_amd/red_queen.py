@@ -121,10 +121,11 @@ class BatchedRedQueen(BatchedPredPreyGrass):
     ``row_id``.  Observations default to float32, the reference's dtype (RQ:352-355)."""
 
     def __init__(self, config, batch_size=1, device=None, obs_dtype=torch.float32, prey_capacity=128, seed=0,
-                 walls=False, _library=None, obs_spread=0):
+                 walls=False, _library=None, obs_spread=0, pred_capacity=64):
         """walls=True selects the walls_occlusion env ("WO"): observation channel 0 shows walls, wall / line-of-sight
         rules for moves and observations (config keys include_visibility_channel, respect_los_for_movement,
-        mask_observation_with_visibility), per-agent move infos in `row_info`.  Walls are given with `set_walls`."""
+        mask_observation_with_visibility), per-agent move infos in `row_info`.  Walls are given with `set_walls`.
+        pred_capacity: 64 or 128 predator rows per env (128: no walls, prey_capacity 128 or 256, one wave per env)."""
         cfg = resolve_config(config)
         self.config = cfg
         self._obs_spread = int(obs_spread)   # (BatchedPredPreyGrass: observation tensors on spread physical pages)
@@ -141,7 +142,7 @@ class BatchedRedQueen(BatchedPredPreyGrass):
         self.n_grass = int(cfg["initial_num_grass"])
         self.cooldown = int(cfg["reproduction_cooldown_steps"])
         self.action_ranges = (int(cfg["type_1_action_range"]), int(cfg["type_2_action_range"]))
-        self._alloc_buffers(prey_capacity)
+        self._alloc_buffers(prey_capacity, pred_capacity)
 
         c = _abi.PpgConfigGen2()
         c.abi_version = _abi.ABI_VERSION
@@ -371,12 +372,17 @@ class PredPreyGrass(_MultiAgentEnvBase):
     _require_all_actions = True    # RQ:279 fails for a live agent without an action
 
     def __init__(self, config=None, *, device=None, prey_capacity: int | None = None, analytics: bool = True,
-                 _check_analytics: bool = False, _library=None):
+                 _check_analytics: bool = False, _library=None, pred_capacity: int | None = None):
         super().__init__()
         cfg = resolve_config(config)
         self.config = config
+        if pred_capacity is None:   # 64 rows; 128 (no walls) on request
+            n_pred = sum(int(cfg[k]) for k in _INITIAL_KEYS[:2])
+            if n_pred > 64 and not self._walls:
+                raise ValueError(f"{n_pred} initial predators exceed the default row capacity of 64: construct the env with pred_capacity=128")
+            pred_capacity = 64
         b = BatchedRedQueen(cfg, batch_size=1, device=device, prey_capacity=prey_capacity or 128, walls=self._walls,
-                            _library=_library)
+                            _library=_library, pred_capacity=pred_capacity)
         self._b = b
         self._cfg = cfg
         for k in ("max_steps", "grid_size", "num_obs_channels", "predator_obs_range", "prey_obs_range",
