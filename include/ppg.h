@@ -460,6 +460,29 @@ typedef struct ppg_fetch_header {
 uint64_t ppg_fetch_bytes(const ppg_handle *h, int32_t n_envs, int64_t n_pred_rows, int64_t n_prey_rows);
 int ppg_fetch(ppg_handle *h, int32_t env0, int32_t n_envs, void *host, uint64_t capacity, void *stream);
 
+/* ---- rows across calls (trajectories from the tensor API) -----------------------------------------------------------
+ * Row order is the API, and it changes with every call: the rows of agents that died are dropped, the newborns of the last call
+ * are merged into sorted position, new newborns are appended.  ppg_link joins the row_id tables of two outputs on the device
+ * (one launch, one wavefront per env; csrc/ppg_link.h) against a library-owned snapshot of what the PREVIOUS ppg_link call of this
+ * handle saw (ids [B,S], PPG_ENV_EPISODE [B], row counts [B,2]; allocated on the first call, freed by ppg_destroy):
+ *   prev_row[b][r]  for a row r in use now: the row its agent had in the snapshot, or -1
+ *   next_row[b][r]  for a row r in use in the snapshot: the row its agent has now, or -1 if it is gone
+ * Both are caller-owned device int16 [B,S]; either may be NULL.  Indices are absolute positions in the [B,S] tables (predators
+ * 0 .. pred_capacity-1, prey from pred_capacity), so gather(x, 1, max(idx, 0)) works directly.  Rows not in use hold -1.  The
+ * call then overwrites the snapshot with the current ids, episode and counts.  -1 cases:
+ *   - a row flagged PPG_ROW_NEWBORN has prev_row -1 (a row flagged PPG_ROW_DIED is still in use: it links to where the agent
+ *     stood, and carries the terminal reward; next_row of a row that had DIED in the snapshot is -1).  This also holds with NO
+ *     step between two ppg_link calls: every other row in use then links to itself, a row still flagged NEWBORN has -1 in both
+ *     maps;
+ *   - an env whose PPG_ENV_EPISODE differs from the snapshot's -- an auto-reset between the two calls -- has -1 everywhere: ids
+ *     restart with every episode ((species, row_id) is unique WITHIN one: csrc/ppg_link.h);
+ *   - the first ppg_link of a handle, and the first after ppg_reset / ppg_reset_from_state (all envs) or after ppg_import_state
+ *     (the imported env only), give -1: those calls invalidate the snapshot on the host.  State written straight into the
+ *     tensors is not seen: call ppg_link once and discard the result.
+ * Any number of steps, or a ppg_rollout of K steps, may lie between two calls: the maps are then the K-step maps (agents born AND
+ * dead in between appear in neither).  Asynchronous on `stream`, ordered behind the handle's last step on that stream. */
+int ppg_link(ppg_handle *h, int16_t *prev_row, int16_t *next_row, void *stream);
+
 /* ---- policy inference next to the env (base_environment/tune_ppo_base_environment.py:106-141) ----------
  * The reference trains two PPO policies (predator_policy / prey_policy) with RLlib's DefaultPPOTorchRLModule and
  * model_config {conv_filters [[16,[3,3],1],[32,[3,3],1],[64,[3,3],1]], fcnet_hiddens [256,256], fcnet_activation relu}.

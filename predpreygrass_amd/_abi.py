@@ -161,7 +161,7 @@ EXPORTED_SYMBOLS = [
     "ppg_rollout", "ppg_step_ordered", "ppg_create_gen2", "ppg_step_uniforms", "ppg_set_envs_in_flight", "ppg_set_wave_plan",
     "ppg_get_wave_plan", "ppg_rebalance",
     "ppg_export_grid", "ppg_walls_changed", "ppg_state_bytes", "ppg_export_state", "ppg_import_state", "ppg_pack_bytes", "ppg_pack",
-    "ppg_fetch_bytes", "ppg_fetch",
+    "ppg_fetch_bytes", "ppg_fetch", "ppg_link",
     "ppg_lexkey", "ppg_lds_bytes", "ppg_step_kernel_name", "ppg_last_error",
 ] + POLICY_SYMBOLS + SPREAD_SYMBOLS
 
@@ -219,6 +219,8 @@ def bind(lib: C.CDLL) -> C.CDLL:
     lib.ppg_fetch_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64]
     lib.ppg_fetch.restype = C.c_int
     lib.ppg_fetch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.ppg_link.restype = C.c_int
+    lib.ppg_link.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(lib, "ppg_alloc_spread"):
         lib.ppg_alloc_spread.restype = C.c_int
         lib.ppg_alloc_spread.argtypes = [C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]

@@ -125,6 +125,7 @@ class BatchedPredPreyGrass:
     # ------------------------------------------------------------------
     def _init_device(self, device, obs_dtype, _library):
         self._emulated = _library is not None
+        self._link_rows = None   # (prev_row, next_row) of link(), allocated on first use
         if _library is None:
             # the product path: HIP on a real GPU, or an exception
             self._lib = _abi.load_hip_library()
@@ -381,6 +382,32 @@ class BatchedPredPreyGrass:
             ptr = C.c_void_p(actions.data_ptr())
         self._check(self._lib.ppg_rollout(self._handle, int(n_steps), ptr, flags, self._stream(stream)), "ppg_rollout")
         return self
+
+    def link(self, stream=None):
+        """Rows of this call's output <-> rows of the output the previous link() saw (`ppg_link`, include/ppg.h): returns
+        (prev_row, next_row), two int16 [B,S] tensors owned by the env and refilled by every call (clone what has to last).
+        prev_row[b, r]: the row the agent in row r had at the previous link(), next_row[b, r]: the row the agent that stood in row r
+        at the previous link() has now; -1 = none (unused row, newborn / gone, another episode, first call or first call after
+        reset / set_placement / import_state).  Indices are absolute row numbers, so
+        ``torch.gather(x, 1, next_row.clamp_min(0).long())`` brings a [B,S] tensor of this call into the previous call's rows.
+        Several steps or a rollout(K) between two calls give the K-step maps; with no step in between every row links to itself,
+        except rows still flagged NEWBORN (-1 in both maps).
+        stream (optional): launch on this torch.cuda.Stream instead of torch's current stream; the two tensors are then allocated
+        on that stream too, and whoever reads them from another stream orders itself behind it."""
+        if self._link_rows is None:
+            def alloc():
+                return tuple(torch.full((self.batch_size, self.S), -1, dtype=torch.int16, device=self.device) for _ in range(2))
+            if self.device.type == "cuda" and hasattr(stream, "cuda_stream"):
+                with torch.cuda.stream(stream):
+                    self._link_rows = alloc()
+            else:
+                self._link_rows = alloc()
+                if self.device.type == "cuda" and stream is not None:   # a raw stream handle: the fill has to be complete before it runs
+                    torch.cuda.current_stream(self.device).synchronize()
+        prev_row, next_row = self._link_rows
+        self._check(self._lib.ppg_link(self._handle, C.c_void_p(prev_row.data_ptr()), C.c_void_p(next_row.data_ptr()),
+                                       self._stream(stream)), "ppg_link")
+        return prev_row, next_row
 
     def export_grid(self):
         """grid_world_state of every env: float64 [B,4,G,G] (predpreygrass_rllib_env.py:124)."""

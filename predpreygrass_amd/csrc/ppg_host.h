@@ -19,6 +19,7 @@
 #include "ppg_kernel.h"
 #include "ppg_pack.h"
 #include "ppg_fetch.h"
+#include "ppg_link.h"
 
 // How a handle's step is scheduled (never what it computes): wavefronts per workgroup, the row count from which helper wavefronts
 // stay, and -- cooperative kernels -- how many envs share a workgroup (0 = one env per workgroup, the ppg[w]_step kernels).
@@ -44,6 +45,8 @@ struct ppg_handle {
     unsigned char *fetch_dev;   // library-owned staging buffer of ppg_fetch (NULL until first used)
     uint64_t fetch_cap;         // its size
     uint64_t fetch_hint;        // bytes the next ppg_fetch copies in its first (usually only) transfer
+    int32_t *link_dev;          // library-owned snapshot of ppg_link: ids [B,S] | episode [B] | row counts [B,2] (NULL until first used)
+    int32_t link_valid;         // the snapshot is one the next ppg_link may link to (0: first call, or a reset since)
     ppg_config cfg;
     ppg_config_gen2 cfg2;
     int32_t gen2;  // created by ppg_create_gen2
@@ -523,6 +526,18 @@ static int backend_pack(ppg_handle *h, const ppg::PackParams &K, void *stream);
 // the launch of ppg_fetch (ppg_fetch.h), and the release of a buffer from backend_alloc
 static int backend_fetch(ppg_handle *h, const ppg::FetchParams &K, void *stream);
 static void backend_free(ppg_handle *h, void *p);
+// the launch of ppg_link (ppg_link.h)
+#ifndef PPG_WAVE_EMU
+static int backend_link(ppg_handle *h, const ppg::LinkParams &K, void *stream);
+#else
+// CPU test build (tests/wave_emu): one single-wave workgroup per env, as on the device.  The test backend's files are frozen (a
+// feature change may only add test files), so this one launch is defined here instead of next to its backend_fetch.
+static void ppg_link_entry(void *arg) { ppg::link_main(*(const ppg::LinkParams *)arg, wv::emu().lds); }
+static int backend_link(ppg_handle *, const ppg::LinkParams &K, void *) {
+    for (int b = 0; b < K.batch; ++b) wv::run_block(ppg_link_entry, (void *)&K, b, ppg::LINK_LDS_BYTES, 1);
+    return PPG_OK;
+}
+#endif
 
 // The state tensors of one env, in image order (include/ppg.h: ppg_state_header): pointer, bytes per env.
 struct ppg_state_field { void *base; size_t bytes; };
@@ -567,6 +582,7 @@ static int ppg_create_common(const ppg_config *cfg, const ppg_config_gen2 *cfg2,
     h->order_dev = nullptr;
     h->vis_dev = nullptr;
     h->fetch_dev = nullptr; h->fetch_cap = 0; h->fetch_hint = 0;
+    h->link_dev = nullptr; h->link_valid = 0;
     h->drive = (cfg && (cfg->n_drive[0] > 0 || cfg->n_drive[1] > 0)) ? 1 : 0;
     int rc = cfg2 ? ppg_validate_and_layout_gen2(h) : ppg_validate_and_layout(h);
     if (rc == PPG_OK) ppg_coop_layout(h);
@@ -597,6 +613,8 @@ int ppg_create_gen2(const ppg_config_gen2 *cfg, int32_t batch, int32_t device, c
 
 int ppg_destroy(ppg_handle *h) {
     if (!h) return PPG_OK;
+    if (h->link_dev) backend_free(h, h->link_dev);
+    h->link_dev = nullptr;
     backend_release(h);
     delete h;
     return PPG_OK;
@@ -606,6 +624,7 @@ int ppg_reset(ppg_handle *h, const uint64_t *seeds, uint32_t episode, void *stre
     if (!h) return PPG_EINVAL;
     ppg::KParams P = h->base;
     P.mode = ppg::MODE_RESET; P.seeds = seeds; P.reset_episode = episode;
+    h->link_valid = 0;   // ids restart and the episode word may repeat: the next ppg_link links nothing
     return backend_launch(h, ppg::MODE_RESET, P, stream);
 }
 
@@ -616,6 +635,7 @@ int ppg_reset_from_state(ppg_handle *h, const ppg_init_state *init, void *stream
     if (!init || !init->grass_xy || (!init->pred_xy && h->cfg.n_initial_predators > 0) || (!init->prey_xy && h->cfg.n_initial_prey > 0))
         return ppg_fail(h, PPG_EINVAL, "ppg_reset_from_state: an array of ppg_init_state is NULL");
     if (h->gen2) return ppg_fail(h, PPG_EINVAL, "ppg_reset_from_state takes base-family handles (second generation: write the tensors, then ppg_observe)");
+    h->link_valid = 0;   // (as in ppg_reset)
     const ppg::KParams &P = h->base;
     const size_t B = (size_t)h->batch, S = (size_t)P.S, NG = (size_t)P.cap_grass;
     const int P0 = h->cfg.n_initial_predators, Q0 = h->cfg.n_initial_prey, n_grass = h->cfg.n_grass, G = P.G;
@@ -944,6 +964,11 @@ int ppg_import_state(ppg_handle *h, int32_t env, const void *blob, uint64_t size
         if (rc != PPG_OK) return rc;
         src += (f[i].bytes + 7) / 8 * 8;
     }
+    if (h->link_dev) {   // ppg_link: env `env` of the snapshot no longer describes the rows in the tensors -- negative row counts
+        static const int32_t none[2] = {-1, -1};
+        const int rc = backend_copy(h, h->link_dev + (size_t)h->batch * h->base.S + h->batch + 2 * (size_t)env, none, sizeof none, true, stream);
+        if (rc != PPG_OK) return rc;
+    }
     {
         const int rc = backend_sync(h, stream);   // the blob may be freed by the caller as soon as this returns
         if (rc != PPG_OK) return rc;
@@ -1070,6 +1095,26 @@ int ppg_fetch(ppg_handle *h, int32_t env0, int32_t n_envs, void *host, uint64_t 
     }
     h->fetch_hint = H->bytes_used + H->bytes_used / 4 + 4096;
     return PPG_OK;
+}
+
+int ppg_link(ppg_handle *h, int16_t *prev_row, int16_t *next_row, void *stream) {
+    if (!h) return PPG_EINVAL;
+    const size_t B = (size_t)h->batch, S = (size_t)h->base.S;
+    if (!h->link_dev) {
+        const int rc = backend_alloc(h, (void **)&h->link_dev, (B * S + B + 2 * B) * sizeof(int32_t));
+        if (rc != PPG_OK) return rc;
+        h->link_valid = 0;   // nothing in it yet: this call writes -1 everywhere and takes the first snapshot
+    }
+    ppg::LinkParams K;
+    memset(&K, 0, sizeof K);
+    K.batch = h->batch; K.S = h->base.S; K.cap_pred = h->base.cap_pred; K.cap_prey = h->base.cap_prey;
+    K.valid = h->link_valid;
+    K.row_id = h->bufs.row_id; K.row_flags = h->bufs.row_flags; K.env_state = h->bufs.env_state;
+    K.snap_id = h->link_dev; K.snap_episode = h->link_dev + B * S; K.snap_rows = h->link_dev + B * S + B;
+    K.prev_row = prev_row; K.next_row = next_row;
+    const int rc = backend_link(h, K, stream);
+    if (rc == PPG_OK) h->link_valid = 1;
+    return rc;
 }
 
 #ifdef PPG_PROFILE_PHASES

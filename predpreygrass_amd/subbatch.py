@@ -174,6 +174,11 @@ class SubBatchedPredPreyGrass:
             e.rebalance(stream=s)
         return self
 
+    def link(self):
+        """`link()` of every sub-batch on its own stream: a list of (prev_row, next_row), one pair per sub-batch (row numbers are
+        per env, so nothing has to be shifted)."""
+        return [e.link(stream=s) for e, s in zip(self.subs, self.streams)]
+
     def rollout(self, n_steps, random_actions=True, auto_reset=False):
         """`n_steps` fused transitions per sub-batch (one launch each, on its own stream)."""
         for e, s in zip(self.subs, self.streams):

@@ -1,0 +1,116 @@
+"""AgentTrajectories: per-agent trajectories from the tensor API, without leaving the device.
+
+The rows of `BatchedPredPreyGrass` / `BatchedRedQueen` change with every call (dead rows are dropped, last call's newborns are
+merged into sorted position, new newborns are appended), so row r of call t + 1 is in general not the agent of row r of call t.
+`env.link()` (`ppg_link`, include/ppg.h) gives the map between two consecutive outputs; this class stores it next to the rewards
+and runs the backward recursions of a learner -- discounted returns, GAE -- through it: one gather per step.
+
+    traj = AgentTrajectories(env, horizon=T)
+    for t in range(T):
+        env.step(actions)            # or random_actions=True, with or without auto_reset
+        traj.record()                # after EVERY step: link() compares with the output the previous record() saw
+    G = traj.returns(0.99)           # float64 [T,B,S]; G[t, b, r] belongs to the agent in row r of call t
+    A = traj.gae(values, 0.99, 0.95)
+
+What it stores per step, in preallocated [T,B,S] device tensors: `reward` (float64), `in_use`, `terminated` (PPG_ROW_DIED),
+`truncated` (PPG_ROW_TRUNC) and `next_row` (int16): the row the agent of row r of call t has in call t + 1, or -1 -- it died, the
+env was reset in between (auto-reset: ids restart, nothing links across episodes), or t is the last recorded step.  An agent's
+successor term is zero where `next_row` is -1 or the row terminated / was truncated in call t:
+
+    G[t] = reward[t] + gamma * G[t + 1][next_row[t]]
+
+so the horizon's last step is treated like an episode end; record one step more than is used to bootstrap from values instead.
+Plain torch: this is bookkeeping, not a hot path (the step and `ppg_link` are).  Not for `SubBatchedPredPreyGrass` as a whole: give
+each sub-batch its own AgentTrajectories.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _abi
+
+
+class AgentTrajectories:
+    def __init__(self, env, horizon):
+        self.env = env
+        self.horizon = int(horizon)
+        if self.horizon < 1:
+            raise ValueError("horizon must be >= 1")
+        T, B, S, dev = self.horizon, env.batch_size, env.S, env.device
+        self.reward = torch.zeros((T, B, S), dtype=torch.float64, device=dev)
+        self.in_use = torch.zeros((T, B, S), dtype=torch.bool, device=dev)
+        self.terminated = torch.zeros((T, B, S), dtype=torch.bool, device=dev)
+        self.truncated = torch.zeros((T, B, S), dtype=torch.bool, device=dev)
+        self.next_row = torch.full((T, B, S), -1, dtype=torch.int16, device=dev)
+        self._slot = torch.arange(S, device=dev, dtype=torch.int32).unsqueeze(0)
+        self.t = 0
+
+    def clear(self):
+        """Start a new trajectory in the same tensors (the next record() is step 0 and links to nothing before it)."""
+        self.t = 0
+        return self
+
+    def __len__(self):
+        return self.t
+
+    def record(self):
+        """Store the output of the env's last call as step t.  Call it after every env.step of the trajectory, on the stream the
+        step ran on (torch's current stream: the link kernel and the copies below are enqueued there)."""
+        if self.t >= self.horizon:
+            raise RuntimeError(f"the trajectory is full ({self.horizon} steps): clear() it")
+        env, t = self.env, self.t
+        _, next_row = env.link()
+        if t > 0:
+            self.next_row[t - 1].copy_(next_row)
+        self.next_row[t].fill_(-1)
+        n_pred = env.env_state[:, _abi.ENV_N_PRED_ROWS:_abi.ENV_N_PRED_ROWS + 1]
+        n_prey = env.env_state[:, _abi.ENV_N_PREY_ROWS:_abi.ENV_N_PREY_ROWS + 1]
+        cp = env.pred_capacity
+        used = torch.where(self._slot < cp, self._slot < n_pred, self._slot - cp < n_prey)
+        self.in_use[t].copy_(used)
+        self.reward[t].copy_(env.row_reward)
+        self.terminated[t].copy_(((env.row_flags & _abi.ROW_DIED) != 0) & used)
+        self.truncated[t].copy_(((env.row_flags & _abi.ROW_TRUNC) != 0) & used)
+        self.t = t + 1
+        return self
+
+    def _successor(self, t, x_next):
+        """x of step t + 1 brought into the rows of step t; 0 where the agent of a row has no successor."""
+        nxt = self.next_row[t]
+        has = (nxt >= 0) & self.in_use[t] & ~self.terminated[t] & ~self.truncated[t]
+        moved = torch.gather(x_next, 1, nxt.clamp_min(0).long())
+        return torch.where(has, moved, torch.zeros_like(moved))
+
+    def returns(self, gamma):
+        """Discounted return of every agent from every step on: float64 [len,B,S], 0 in rows not in use."""
+        n = self.t
+        G = torch.zeros((n,) + tuple(self.reward.shape[1:]), dtype=torch.float64, device=self.reward.device)
+        g_next = torch.zeros_like(G[0]) if n else None
+        zero = torch.zeros_like(G[0]) if n else None
+        for t in range(n - 1, -1, -1):
+            succ = self._successor(t, g_next) if t + 1 < n else zero
+            g = self.reward[t] + succ * float(gamma)   # (two roundings, mul then add: what float64 Python arithmetic does)
+            g_next = torch.where(self.in_use[t], g, zero)
+            G[t] = g_next
+        return G
+
+    def gae(self, values, gamma, lam):
+        """Generalised advantage estimate: delta[t] = reward[t] + gamma * V[t + 1][next_row[t]] - V[t],
+        A[t] = delta[t] + gamma * lam * A[t + 1][next_row[t]], successor terms zero where there is no successor.
+        values: [len,B,S] (any float dtype; row r of values[t] = the agent in row r of call t).  Returns float64 [len,B,S]."""
+        n = self.t
+        if tuple(values.shape) != (n,) + tuple(self.reward.shape[1:]):
+            raise ValueError(f"values must be [{n},{self.reward.shape[1]},{self.reward.shape[2]}]")
+        V = values.to(device=self.reward.device, dtype=torch.float64)
+        A = torch.zeros_like(V)
+        zero = torch.zeros_like(V[0]) if n else None
+        a_next = zero
+        gl = float(gamma) * float(lam)
+        for t in range(n - 1, -1, -1):
+            v_succ = self._successor(t, V[t + 1]) if t + 1 < n else zero
+            a_succ = self._successor(t, a_next) if t + 1 < n else zero
+            delta = (self.reward[t] + v_succ * float(gamma)) - V[t]
+            a = delta + a_succ * gl
+            a_next = torch.where(self.in_use[t], a, zero)
+            A[t] = a_next
+        return A
