@@ -154,14 +154,18 @@ def compare_env_with_oracle(env: BatchedPredPreyGrass, b, orc, tables, check_obs
     assert ((gx >> 8) == gxy[:, 0]).all() and ((gx & 255) == gxy[:, 1]).all(), (tag, b, "grass xy")
     if check_obs:
         o = orc._out
-        op = env.obs_pred[b].cpu().numpy()
-        oq = env.obs_prey[b].cpu().numpy()
+        bf16 = env.obs_pred.dtype == torch.bfloat16   # numpy has no such dtype: the rows are compared as int16 bit patterns
+        op = (env.obs_pred[b].view(torch.int16) if bf16 else env.obs_pred[b]).cpu().numpy()
+        oq = (env.obs_prey[b].view(torch.int16) if bf16 else env.obs_prey[b]).cpu().numpy()
         for k, (name, ty, row, _, _, _) in enumerate(recs):
             r = o.records[k]
             want = np.ctypeslib.as_array(o.obs, shape=(r.obs_offset + r.obs_len,))[r.obs_offset:]
             got = (op if ty == PREDATOR else oq)[row].reshape(-1)
             if got.dtype == np.float64:
                 assert got.tobytes() == want.tobytes(), (tag, b, name, "obs")
+            elif bf16:   # round-to-nearest-even of the float32 of the float64 value (test_bfloat16_observation_rows_are_the_rounded_float64_rows)
+                w = torch.from_numpy(np.array(want)).float().bfloat16().view(torch.int16).numpy()
+                assert got.tobytes() == w.tobytes(), (tag, b, name, "obs bf16")
             else:
                 assert (got == want.astype(np.float32)).all(), (tag, b, name, "obs f32")
 

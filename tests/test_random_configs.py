@@ -52,9 +52,9 @@ def random_placement(rng, cfg):
     return xy[:P], xy[P:P + Q], xy[P + Q:]
 
 
-def run_differential(make_env, seed, max_calls=45):
+def run_differential(make_env, seed, max_calls=45, config_fn=random_config):
     rng = np.random.default_rng(seed)
-    cfg = random_config(rng)
+    cfg = config_fn(rng)
     placement = random_placement(rng, cfg)
     env = make_env(cfg)
     orc = OracleEnv(cfg)

@@ -69,9 +69,9 @@ def random_placement(rng, cfg, n_extra=0):
     return xy[:P], xy[P:P + Q], xy[P + Q:]
 
 
-def run_differential(make_env, seed, max_calls=45, walls=False):
+def run_differential(make_env, seed, max_calls=45, walls=False, config_fn=random_config):
     rng = np.random.default_rng(1000 + seed + (7777 if walls else 0))
-    cfg = random_config(rng)
+    cfg = config_fn(rng)
     wall_xy = []
     if walls:   # walls_occlusion env: random walls (placement avoids them), random line-of-sight options
         G = cfg["grid_size"]
