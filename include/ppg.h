@@ -483,6 +483,34 @@ int ppg_fetch(ppg_handle *h, int32_t env0, int32_t n_envs, void *host, uint64_t 
  * dead in between appear in neither).  Asynchronous on `stream`, ordered behind the handle's last step on that stream. */
 int ppg_link(ppg_handle *h, int16_t *prev_row, int16_t *next_row, void *stream);
 
+/* ---- returns and advantages over a recorded horizon ------------------------------------------------------------------
+ * What a learner does with the maps of ppg_link: the backward recursions over n_steps recorded calls, discounted returns G and
+ * generalised advantages A, in ONE launch (one wavefront per env, the values of step t + 1 in LDS; csrc/ppg_backward.h).  All
+ * tensors are caller-owned, contiguous device [n_steps,B,S] (B and S are the handle's): reward float64, next_row int16 (the
+ * next_row of the ppg_link call that followed step t), in_use / terminated / truncated uint8 0 / 1 (what a bool tensor holds),
+ * values float64 (PPG_F64) or float32 (PPG_F32, widened exactly), returns / advantages float64.  For t = n_steps-1 .. 0 and
+ * every row r of env b, each line one IEEE float64 operation in this order, no fused multiply-add:
+ *   has    = t + 1 < n_steps && in_use[t][r] && !terminated[t][r] && !truncated[t][r] && 0 <= next_row[t][r] < S
+ *   g_succ = has ? G[t+1][next_row[t][r]] : 0.0          (likewise a_succ from A[t+1], v_succ from values[t+1])
+ *   G[t][r] = in_use ? reward + g_succ * gamma : 0.0
+ *   A[t][r] = in_use ? ((reward + v_succ * gamma) - values[t][r]) + a_succ * (gamma * lam) : 0.0
+ * gamma * lam is formed once in double on the host.  The call touches no env state and no library-owned buffer, and writes
+ * every element of the outputs it is given.  Cases:
+ *   - returns or advantages may be NULL (not both); advantages need values, returns alone ignore them (values may be NULL);
+ *   - absent terms are selected, never multiplied away: a NaN or any other word in a row not in use, or in a successor slot that
+ *     is not taken, reaches no output; rows not in use get +0.0.  The add of 0.0 * gamma still happens where there is no
+ *     successor (a reward of -0.0 gives +0.0);
+ *   - a next_row outside [0, S) means "no successor" like -1: no value from a tensor is used as an index unchecked;
+ *   - the last step has no successor at all: the horizon's end is treated like an episode's;
+ *   - PPG_EINVAL (text in ppg_last_error): n_steps < 1, a NULL input, both outputs NULL, advantages without values, a
+ *     values_dtype that is neither code, a handle whose S is not 64 * (2 .. 6); nothing is launched then.
+ * Asynchronous on `stream`. */
+#define PPG_F64 0
+#define PPG_F32 1
+int ppg_backward(ppg_handle *h, int32_t n_steps, const double *reward, const int16_t *next_row, const uint8_t *in_use,
+                 const uint8_t *terminated, const uint8_t *truncated, const void *values, int32_t values_dtype, /* values may be NULL */
+                 double gamma, double lam, double *returns, double *advantages, void *stream);
+
 /* ---- policy inference next to the env (base_environment/tune_ppo_base_environment.py:106-141) ----------
  * The reference trains two PPO policies (predator_policy / prey_policy) with RLlib's DefaultPPOTorchRLModule and
  * model_config {conv_filters [[16,[3,3],1],[32,[3,3],1],[64,[3,3],1]], fcnet_hiddens [256,256], fcnet_activation relu}.

@@ -15,6 +15,8 @@ ABI_VERSION = 5
 
 # row_flags bits
 ROW_DIED, ROW_OWNS, ROW_NEWBORN, ROW_ATE, ROW_TRUNC, ROW_GRID_E0 = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+# dtype codes of ppg_backward's `values`
+F64, F32 = 0, 1
 # env_state words
 ENV_WORDS = 20
 (ENV_N_PRED_ROWS, ENV_N_PREY_ROWS, ENV_N_PRED_NEW, ENV_N_PREY_NEW, ENV_NEXT_PRED_ID, ENV_NEXT_PREY_ID,
@@ -161,7 +163,7 @@ EXPORTED_SYMBOLS = [
     "ppg_rollout", "ppg_step_ordered", "ppg_create_gen2", "ppg_step_uniforms", "ppg_set_envs_in_flight", "ppg_set_wave_plan",
     "ppg_get_wave_plan", "ppg_rebalance",
     "ppg_export_grid", "ppg_walls_changed", "ppg_state_bytes", "ppg_export_state", "ppg_import_state", "ppg_pack_bytes", "ppg_pack",
-    "ppg_fetch_bytes", "ppg_fetch", "ppg_link",
+    "ppg_fetch_bytes", "ppg_fetch", "ppg_link", "ppg_backward",
     "ppg_lexkey", "ppg_lds_bytes", "ppg_step_kernel_name", "ppg_last_error",
 ] + POLICY_SYMBOLS + SPREAD_SYMBOLS
 
@@ -221,6 +223,9 @@ def bind(lib: C.CDLL) -> C.CDLL:
     lib.ppg_fetch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.ppg_link.restype = C.c_int
     lib.ppg_link.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ppg_backward.restype = C.c_int
+    lib.ppg_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,   # handle, n_steps, five inputs
+                                 C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]   # values, dtype, gamma, lam, G, A, stream
     if hasattr(lib, "ppg_alloc_spread"):
         lib.ppg_alloc_spread.restype = C.c_int
         lib.ppg_alloc_spread.argtypes = [C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]

@@ -409,6 +409,51 @@ class BatchedPredPreyGrass:
                                        self._stream(stream)), "ppg_link")
         return prev_row, next_row
 
+    def backward(self, reward, next_row, in_use, terminated, truncated, gamma, lam=1.0, values=None, returns=True,
+                 advantages=None, stream=None):
+        """Discounted returns and generalised advantages over a recorded horizon in ONE launch (`ppg_backward`, include/ppg.h:
+        the recursion and its cases are stated there).  All inputs are contiguous [T,B,S] tensors on the env's device: reward
+        float64, next_row int16 (`link()`'s next_row of the call after step t), in_use / terminated / truncated bool (or uint8
+        0 / 1), values float64 or float32 (only needed for advantages).  Returns (G, A), float64 [T,B,S] each, newly allocated;
+        the one not asked for (`returns=False`; `advantages` defaults to "values were given") is None.  The env's state is not
+        touched: the handle only supplies B, S and the device.
+        stream (optional): as in link() -- the launch and the allocation of the outputs go to that stream."""
+        want_a = (values is not None) if advantages is None else bool(advantages)
+        if not returns and not want_a:
+            raise ValueError("backward: neither returns nor advantages asked for")
+        if want_a and values is None:
+            raise ValueError("backward: advantages need values")
+        if reward.dim() != 3 or reward.shape[0] < 1 or tuple(reward.shape[1:]) != (self.batch_size, self.S):
+            raise ValueError(f"reward must be [T,{self.batch_size},{self.S}] with T >= 1, not {tuple(reward.shape)}")
+        shape = tuple(reward.shape)
+        flag = (torch.bool, torch.uint8)
+        tensors = [("reward", reward, (torch.float64,)), ("next_row", next_row, (torch.int16,)), ("in_use", in_use, flag),
+                   ("terminated", terminated, flag), ("truncated", truncated, flag)]
+        if want_a:
+            tensors.append(("values", values, (torch.float64, torch.float32)))
+        for name, x, dtypes in tensors:
+            if x.dtype not in dtypes or tuple(x.shape) != shape or x.device != self.device or not x.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {' / '.join(str(d) for d in dtypes)} tensor {list(shape)} on "
+                                 f"{self.device}, not {x.dtype} {list(x.shape)} on {x.device}")
+
+        def alloc():
+            return tuple(torch.empty(shape, dtype=torch.float64, device=self.device) if want else None for want in (returns, want_a))
+        if self.device.type == "cuda" and hasattr(stream, "cuda_stream"):
+            with torch.cuda.stream(stream):
+                G, A = alloc()
+        else:
+            G, A = alloc()
+            if self.device.type == "cuda" and stream is not None:   # a raw stream handle: the block may still be in use on torch's stream
+                torch.cuda.current_stream(self.device).synchronize()
+
+        def ptr(x):
+            return None if x is None else C.c_void_p(x.data_ptr())
+        self._check(self._lib.ppg_backward(self._handle, shape[0], ptr(reward), ptr(next_row), ptr(in_use), ptr(terminated),
+                                           ptr(truncated), ptr(values) if want_a else None,
+                                           _abi.F32 if want_a and values.dtype == torch.float32 else _abi.F64,
+                                           float(gamma), float(lam), ptr(G), ptr(A), self._stream(stream)), "ppg_backward")
+        return G, A
+
     def export_grid(self):
         """grid_world_state of every env: float64 [B,4,G,G] (predpreygrass_rllib_env.py:124)."""
         G = self.grid_size

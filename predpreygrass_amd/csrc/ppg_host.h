@@ -20,6 +20,7 @@
 #include "ppg_pack.h"
 #include "ppg_fetch.h"
 #include "ppg_link.h"
+#include "ppg_backward.h"
 
 // How a handle's step is scheduled (never what it computes): wavefronts per workgroup, the row count from which helper wavefronts
 // stay, and -- cooperative kernels -- how many envs share a workgroup (0 = one env per workgroup, the ppg[w]_step kernels).
@@ -47,6 +48,7 @@ struct ppg_handle {
     uint64_t fetch_hint;        // bytes the next ppg_fetch copies in its first (usually only) transfer
     int32_t *link_dev;          // library-owned snapshot of ppg_link: ids [B,S] | episode [B] | row counts [B,2] (NULL until first used)
     int32_t link_valid;         // the snapshot is one the next ppg_link may link to (0: first call, or a reset since)
+    int32_t backward_prefetch;  // ppg_backward requests step t - 1's inputs before step t's gather (PPG_BACKWARD_PREFETCH, read at create)
     ppg_config cfg;
     ppg_config_gen2 cfg2;
     int32_t gen2;  // created by ppg_create_gen2
@@ -538,6 +540,17 @@ static int backend_link(ppg_handle *, const ppg::LinkParams &K, void *) {
     return PPG_OK;
 }
 #endif
+// the launch of ppg_backward (ppg_backward.h)
+#ifndef PPG_WAVE_EMU
+static int backend_backward(ppg_handle *h, const ppg::BackwardParams &K, void *stream);
+#else
+// (CPU test build: defined here for the same reason as backend_link)
+static void ppg_backward_entry(void *arg) { ppg::backward_main(*(const ppg::BackwardParams *)arg, wv::emu().lds); }
+static int backend_backward(ppg_handle *, const ppg::BackwardParams &K, void *) {
+    for (int b = 0; b < K.batch; ++b) wv::run_block(ppg_backward_entry, (void *)&K, b, ppg::BACKWARD_LDS_BYTES, 1);
+    return PPG_OK;
+}
+#endif
 
 // The state tensors of one env, in image order (include/ppg.h: ppg_state_header): pointer, bytes per env.
 struct ppg_state_field { void *base; size_t bytes; };
@@ -578,6 +591,8 @@ static int ppg_create_common(const ppg_config *cfg, const ppg_config_gen2 *cfg2,
         const char *ev = getenv("PPG_COOP_WGS_PER_CU"), *pad = getenv("PPG_STEP_LDS_PAD");
         h->coop_wgs_per_cu = ev ? atoi(ev) : 5;
         h->step_lds_pad = pad ? atoi(pad) : 0;
+        const char *pf = getenv("PPG_BACKWARD_PREFETCH");   // (A/B of ppg_backward's load placement: profiles/EXPERIMENTS.md)
+        h->backward_prefetch = pf ? (atoi(pf) != 0) : 1;
     }
     h->order_dev = nullptr;
     h->vis_dev = nullptr;
@@ -1115,6 +1130,30 @@ int ppg_link(ppg_handle *h, int16_t *prev_row, int16_t *next_row, void *stream) 
     const int rc = backend_link(h, K, stream);
     if (rc == PPG_OK) h->link_valid = 1;
     return rc;
+}
+
+int ppg_backward(ppg_handle *h, int32_t n_steps, const double *reward, const int16_t *next_row, const uint8_t *in_use,
+                 const uint8_t *terminated, const uint8_t *truncated, const void *values, int32_t values_dtype, double gamma, double lam,
+                 double *returns, double *advantages, void *stream) {
+    if (!h) return PPG_EINVAL;
+    if (n_steps < 1) return ppg_fail(h, PPG_EINVAL, "ppg_backward: n_steps %d < 1", n_steps);
+    if (!reward || !next_row || !in_use || !terminated || !truncated) return ppg_fail(h, PPG_EINVAL, "ppg_backward: an input pointer is NULL");
+    if (!returns && !advantages) return ppg_fail(h, PPG_EINVAL, "ppg_backward: returns and advantages are both NULL");
+    if (advantages && !values) return ppg_fail(h, PPG_EINVAL, "ppg_backward: advantages need values");
+    if (values && values_dtype != PPG_F64 && values_dtype != PPG_F32)
+        return ppg_fail(h, PPG_EINVAL, "ppg_backward: values_dtype %d is neither PPG_F64 nor PPG_F32", values_dtype);
+    const int S = h->base.S;
+    if (S % 64 != 0 || S < 128 || S * 8 * 3 > ppg::BACKWARD_LDS_BYTES)   // the kernel's instantiations: 2 .. 6 row registers per lane
+        return ppg_fail(h, PPG_EINVAL, "ppg_backward: %d rows per env (needs a multiple of 64 in 128..%d)", S, ppg::BACKWARD_MAX_ROWS);
+    ppg::BackwardParams K;
+    memset(&K, 0, sizeof K);
+    K.batch = h->batch; K.S = S; K.T = n_steps;
+    K.values_f32 = values && values_dtype == PPG_F32; K.prefetch = h->backward_prefetch;
+    K.reward = reward; K.next_row = next_row; K.in_use = in_use; K.terminated = terminated; K.truncated = truncated;
+    K.values = advantages ? values : nullptr;
+    K.gamma = gamma; K.gl = gamma * lam;
+    K.returns = returns; K.advantages = advantages;
+    return backend_backward(h, K, stream);
 }
 
 #ifdef PPG_PROFILE_PHASES

@@ -3,7 +3,8 @@
 The rows of `BatchedPredPreyGrass` / `BatchedRedQueen` change with every call (dead rows are dropped, last call's newborns are
 merged into sorted position, new newborns are appended), so row r of call t + 1 is in general not the agent of row r of call t.
 `env.link()` (`ppg_link`, include/ppg.h) gives the map between two consecutive outputs; this class stores it next to the rewards
-and runs the backward recursions of a learner -- discounted returns, GAE -- through it: one gather per step.
+and runs the backward recursions of a learner -- discounted returns, GAE -- through it: one gather per step, the whole horizon in
+one kernel launch (`env.backward()`, `ppg_backward`).
 
     traj = AgentTrajectories(env, horizon=T)
     for t in range(T):
@@ -11,6 +12,7 @@ and runs the backward recursions of a learner -- discounted returns, GAE -- thro
         traj.record()                # after EVERY step: link() compares with the output the previous record() saw
     G = traj.returns(0.99)           # float64 [T,B,S]; G[t, b, r] belongs to the agent in row r of call t
     A = traj.gae(values, 0.99, 0.95)
+    G, A = traj.returns_and_gae(values, 0.99, 0.95)   # both in ONE launch
 
 What it stores per step, in preallocated [T,B,S] device tensors: `reward` (float64), `in_use`, `terminated` (PPG_ROW_DIED),
 `truncated` (PPG_ROW_TRUNC) and `next_row` (int16): the row the agent of row r of call t has in call t + 1, or -1 -- it died, the
@@ -20,8 +22,12 @@ successor term is zero where `next_row` is -1 or the row terminated / was trunca
     G[t] = reward[t] + gamma * G[t + 1][next_row[t]]
 
 so the horizon's last step is treated like an episode end; record one step more than is used to bootstrap from values instead.
-Plain torch: this is bookkeeping, not a hot path (the step and `ppg_link` are).  Not for `SubBatchedPredPreyGrass` as a whole: give
-each sub-batch its own AgentTrajectories.
+The recursions run in the `ppg_backward` kernel (csrc/ppg_backward.h: one wavefront per env, step t + 1 in LDS): as a torch loop
+over the horizon -- about ten small launches per step, kept verbatim as `returns_torch()` / `gae_torch()` -- GAE over 128 steps of
+4096 envs took 20.8 ms, twice the rollout it post-processes, against 0.56 ms (profiles/EXPERIMENTS.md, `ppg_backward`); both give the
+same bits.  Recording
+(`record()`) stays plain torch copies behind `ppg_link`.  Not for `SubBatchedPredPreyGrass` as a whole: give each sub-batch its own
+AgentTrajectories.
 """
 from __future__ import annotations
 
@@ -81,8 +87,39 @@ class AgentTrajectories:
         moved = torch.gather(x_next, 1, nxt.clamp_min(0).long())
         return torch.where(has, moved, torch.zeros_like(moved))
 
+    def _backward(self, values, gamma, lam, returns):
+        """The first len(self) steps of the stored tensors (a contiguous prefix) through env.backward()."""
+        n = self.t
+        B, S = self.reward.shape[1:]
+        if values is not None:
+            if tuple(values.shape) != (n, B, S):
+                raise ValueError(f"values must be [{n},{B},{S}]")
+            if values.dtype not in (torch.float64, torch.float32):
+                values = values.to(torch.float32)   # (exact for bfloat16 / float16)
+            values = values.to(self.reward.device).contiguous()
+        if n == 0:
+            empty = torch.zeros((0, B, S), dtype=torch.float64, device=self.reward.device)
+            return (empty if returns else None), (empty.clone() if values is not None else None)
+        return self.env.backward(self.reward[:n], self.next_row[:n], self.in_use[:n], self.terminated[:n], self.truncated[:n],
+                                 gamma, lam, values=values, returns=returns)
+
     def returns(self, gamma):
         """Discounted return of every agent from every step on: float64 [len,B,S], 0 in rows not in use."""
+        return self._backward(None, gamma, 1.0, True)[0]
+
+    def gae(self, values, gamma, lam):
+        """Generalised advantage estimate: delta[t] = reward[t] + gamma * V[t + 1][next_row[t]] - V[t],
+        A[t] = delta[t] + gamma * lam * A[t + 1][next_row[t]], successor terms zero where there is no successor.
+        values: [len,B,S] (float64 / float32 as they are, any other float dtype through float32; row r of values[t] = the agent in
+        row r of call t).  Returns float64 [len,B,S]."""
+        return self._backward(values, gamma, lam, False)[1]
+
+    def returns_and_gae(self, values, gamma, lam):
+        """(returns(gamma), gae(values, gamma, lam)) in ONE launch."""
+        return self._backward(values, gamma, lam, True)
+
+    def returns_torch(self, gamma):
+        """returns() as a torch loop over the steps: the same bits, about five launches per step (timing baseline, fallback)."""
         n = self.t
         G = torch.zeros((n,) + tuple(self.reward.shape[1:]), dtype=torch.float64, device=self.reward.device)
         g_next = torch.zeros_like(G[0]) if n else None
@@ -94,10 +131,8 @@ class AgentTrajectories:
             G[t] = g_next
         return G
 
-    def gae(self, values, gamma, lam):
-        """Generalised advantage estimate: delta[t] = reward[t] + gamma * V[t + 1][next_row[t]] - V[t],
-        A[t] = delta[t] + gamma * lam * A[t + 1][next_row[t]], successor terms zero where there is no successor.
-        values: [len,B,S] (any float dtype; row r of values[t] = the agent in row r of call t).  Returns float64 [len,B,S]."""
+    def gae_torch(self, values, gamma, lam):
+        """gae() as a torch loop over the steps: the same bits (timing baseline, fallback).  values: any float dtype."""
         n = self.t
         if tuple(values.shape) != (n,) + tuple(self.reward.shape[1:]):
             raise ValueError(f"values must be [{n},{self.reward.shape[1]},{self.reward.shape[2]}]")
