@@ -483,6 +483,37 @@ int ppg_fetch(ppg_handle *h, int32_t env0, int32_t n_envs, void *host, uint64_t 
  * dead in between appear in neither).  Asynchronous on `stream`, ordered behind the handle's last step on that stream. */
 int ppg_link(ppg_handle *h, int16_t *prev_row, int16_t *next_row, void *stream);
 
+/* ---- one step into trajectory buffers ---------------------------------------------------------------------------------
+ * ppg_record is ppg_link(h, prev_row, next_row, stream) PLUS the stores that keep the output of the handle's last call as step t
+ * of a trajectory, in the same launch (one wavefront per env; csrc/ppg_record.h).  It IS a link call: it uses and overwrites the
+ * same library-owned snapshot, prev_row / next_row (either may be NULL) are written exactly as by ppg_link, every -1 case above
+ * holds, and ppg_link and ppg_record calls may be mixed freely.  The buffers of ppg_record_buffers are caller-owned, contiguous
+ * device tensors [horizon,B,S] (B and S are the handle's), the inputs of ppg_backward.  For every row r of every env b:
+ *   next_row[t-1][b][r] = the link's next_row[b][r]                      -- only if t > 0
+ *   next_row[t][b][r]   = -1
+ *   reward[t][b][r]     = the bits of row_reward[b][r]                    -- all S rows, in use or not
+ *   in_use[t][b][r]     = r < pred_capacity ? r < n_pred_rows : r - pred_capacity < n_prey_rows          (uint8 0 / 1)
+ *   terminated[t][b][r] = in_use && (row_flags[b][r] & PPG_ROW_DIED)      truncated: likewise with PPG_ROW_TRUNC
+ * and no other element of the buffers is touched.  The step index t:
+ *   flags == 0                      t = step.  A step outside [0, horizon) is PPG_EINVAL.
+ *   PPG_RECORD_STEP_ON_DEVICE       `step` is the address of an int32 in DEVICE memory that the kernel reads when it runs: a step
+ *                                   captured into a hipGraph (ppg_step + ppg_record + an increment of that word) can be replayed.
+ *                                   If the word is outside [0, horizon) when the kernel runs, the launch behaves exactly like
+ *                                   ppg_link(h, prev_row, next_row): the snapshot advances, no buffer is written -- a replay past
+ *                                   the horizon cannot write out of bounds (the word becomes an index only after that check).
+ * PPG_EINVAL (text in ppg_last_error, nothing is launched, the snapshot is untouched): buf NULL, one of the five buffers NULL,
+ * horizon < 1, a host step outside [0, horizon), a NULL device address, unknown flag bits.  Asynchronous on `stream`, ordered
+ * behind the handle's last step on that stream. */
+typedef struct ppg_record_buffers {
+    int32_t horizon;       /* T */
+    double *reward;        /* [T,B,S] */
+    uint8_t *in_use, *terminated, *truncated;   /* [T,B,S], 0 / 1 (what a bool tensor holds) */
+    int16_t *next_row;     /* [T,B,S] */
+} ppg_record_buffers;
+#define PPG_RECORD_STEP_ON_DEVICE 0x1u
+int ppg_record(ppg_handle *h, const ppg_record_buffers *buf, uint64_t step, uint32_t flags, int16_t *prev_row, int16_t *next_row,
+               void *stream);
+
 /* ---- returns and advantages over a recorded horizon ------------------------------------------------------------------
  * What a learner does with the maps of ppg_link: the backward recursions over n_steps recorded calls, discounted returns G and
  * generalised advantages A, in ONE launch (one wavefront per env, the values of step t + 1 in LDS; csrc/ppg_backward.h).  All

@@ -17,6 +17,8 @@ ABI_VERSION = 5
 ROW_DIED, ROW_OWNS, ROW_NEWBORN, ROW_ATE, ROW_TRUNC, ROW_GRID_E0 = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
 # dtype codes of ppg_backward's `values`
 F64, F32 = 0, 1
+# flags of ppg_record
+RECORD_STEP_ON_DEVICE = 0x1
 # env_state words
 ENV_WORDS = 20
 (ENV_N_PRED_ROWS, ENV_N_PREY_ROWS, ENV_N_PRED_NEW, ENV_N_PREY_NEW, ENV_NEXT_PRED_ID, ENV_NEXT_PREY_ID,
@@ -127,6 +129,12 @@ class PpgBuffers(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in _BUF_FIELDS]
 
 
+class PpgRecordBuffers(C.Structure):
+    """include/ppg.h: struct ppg_record_buffers (device tensors [horizon,B,S])."""
+    _fields_ = [("horizon", C.c_int32), ("reward", C.c_void_p), ("in_use", C.c_void_p), ("terminated", C.c_void_p),
+                ("truncated", C.c_void_p), ("next_row", C.c_void_p)]
+
+
 class PpgInitState(C.Structure):
     """include/ppg.h: struct ppg_init_state (host uint16 arrays, cells as (x << 8) | y)."""
     _fields_ = [("pred_xy", C.c_void_p), ("prey_xy", C.c_void_p), ("grass_xy", C.c_void_p), ("episode", C.c_uint32), ("reserved_", C.c_uint32)]
@@ -163,7 +171,7 @@ EXPORTED_SYMBOLS = [
     "ppg_rollout", "ppg_step_ordered", "ppg_create_gen2", "ppg_step_uniforms", "ppg_set_envs_in_flight", "ppg_set_wave_plan",
     "ppg_get_wave_plan", "ppg_rebalance",
     "ppg_export_grid", "ppg_walls_changed", "ppg_state_bytes", "ppg_export_state", "ppg_import_state", "ppg_pack_bytes", "ppg_pack",
-    "ppg_fetch_bytes", "ppg_fetch", "ppg_link", "ppg_backward",
+    "ppg_fetch_bytes", "ppg_fetch", "ppg_link", "ppg_record", "ppg_backward",
     "ppg_lexkey", "ppg_lds_bytes", "ppg_step_kernel_name", "ppg_last_error",
 ] + POLICY_SYMBOLS + SPREAD_SYMBOLS
 
@@ -223,6 +231,8 @@ def bind(lib: C.CDLL) -> C.CDLL:
     lib.ppg_fetch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.ppg_link.restype = C.c_int
     lib.ppg_link.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ppg_record.restype = C.c_int
+    lib.ppg_record.argtypes = [C.c_void_p, C.POINTER(PpgRecordBuffers), C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ppg_backward.restype = C.c_int
     lib.ppg_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,   # handle, n_steps, five inputs
                                  C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]   # values, dtype, gamma, lam, G, A, stream

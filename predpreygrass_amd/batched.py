@@ -394,6 +394,13 @@ class BatchedPredPreyGrass:
         except rows still flagged NEWBORN (-1 in both maps).
         stream (optional): launch on this torch.cuda.Stream instead of torch's current stream; the two tensors are then allocated
         on that stream too, and whoever reads them from another stream orders itself behind it."""
+        prev_row, next_row = self._link_tensors(stream)
+        self._check(self._lib.ppg_link(self._handle, C.c_void_p(prev_row.data_ptr()), C.c_void_p(next_row.data_ptr()),
+                                       self._stream(stream)), "ppg_link")
+        return prev_row, next_row
+
+    def _link_tensors(self, stream=None):
+        """The env's (prev_row, next_row) of link() / record(), allocated on first use."""
         if self._link_rows is None:
             def alloc():
                 return tuple(torch.full((self.batch_size, self.S), -1, dtype=torch.int16, device=self.device) for _ in range(2))
@@ -404,10 +411,39 @@ class BatchedPredPreyGrass:
                 self._link_rows = alloc()
                 if self.device.type == "cuda" and stream is not None:   # a raw stream handle: the fill has to be complete before it runs
                     torch.cuda.current_stream(self.device).synchronize()
-        prev_row, next_row = self._link_rows
-        self._check(self._lib.ppg_link(self._handle, C.c_void_p(prev_row.data_ptr()), C.c_void_p(next_row.data_ptr()),
-                                       self._stream(stream)), "ppg_link")
-        return prev_row, next_row
+        return self._link_rows
+
+    def record(self, reward, in_use, terminated, truncated, next_row, t, stream=None):
+        """link() plus the stores that keep this call's output as step t of a trajectory, in ONE launch (`ppg_record`,
+        include/ppg.h: the elements written are stated there).  The five buffers are contiguous [T,B,S] tensors on the env's device,
+        the inputs of backward(): reward float64, in_use / terminated / truncated bool (or uint8), next_row int16.
+        t: an int in [0, T), or a one-element int32 tensor on the env's device that the kernel reads when it runs (a captured
+        step + record can then be replayed while the graph counts the tensor up); if that word is outside [0, T) the call is
+        link() and writes no buffer.  Returns link()'s (prev_row, next_row): the env's own tensors, written exactly as by link().
+        stream (optional): as in link()."""
+        if reward.dim() != 3 or reward.shape[0] < 1 or tuple(reward.shape[1:]) != (self.batch_size, self.S):
+            raise ValueError(f"reward must be [T,{self.batch_size},{self.S}] with T >= 1, not {tuple(reward.shape)}")
+        shape = tuple(reward.shape)
+        flag = (torch.bool, torch.uint8)
+        for name, x, dtypes in (("reward", reward, (torch.float64,)), ("in_use", in_use, flag), ("terminated", terminated, flag),
+                                ("truncated", truncated, flag), ("next_row", next_row, (torch.int16,))):
+            if x.dtype not in dtypes or tuple(x.shape) != shape or x.device != self.device or not x.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {' / '.join(str(d) for d in dtypes)} tensor {list(shape)} on "
+                                 f"{self.device}, not {x.dtype} {list(x.shape)} on {x.device}")
+        if isinstance(t, torch.Tensor):
+            if t.dtype != torch.int32 or t.numel() != 1 or t.device != self.device:
+                raise ValueError(f"t must be an int or a one-element int32 tensor on {self.device}")
+            step, flags = t.data_ptr(), _abi.RECORD_STEP_ON_DEVICE
+        else:
+            step, flags = int(t), 0
+            if not 0 <= step < shape[0]:
+                raise ValueError(f"t = {step} is outside [0, {shape[0]})")
+        buf = _abi.PpgRecordBuffers(shape[0], reward.data_ptr(), in_use.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
+                                    next_row.data_ptr())
+        prev_row, link_next = self._link_tensors(stream)
+        self._check(self._lib.ppg_record(self._handle, C.byref(buf), step, flags, C.c_void_p(prev_row.data_ptr()),
+                                         C.c_void_p(link_next.data_ptr()), self._stream(stream)), "ppg_record")
+        return prev_row, link_next
 
     def backward(self, reward, next_row, in_use, terminated, truncated, gamma, lam=1.0, values=None, returns=True,
                  advantages=None, stream=None):

@@ -247,6 +247,20 @@ static int backend_link(ppg_handle *h, const ppg::LinkParams &K, void *stream) {
     return PPG_OK;
 }
 
+// ---- ppg_record: the link plus one step's stores into trajectory buffers (ppg_record.h) ----------------------------
+extern "C" __global__ void __launch_bounds__(64) ppg_record_rows(const ppg::RecordParams K) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[ppg::LINK_LDS_BYTES];
+    ppg::record_main(*PPG_KERNARG_PTR(ppg::RecordParams, K), lds);
+}
+
+static int backend_record(ppg_handle *h, const ppg::RecordParams &K, void *stream) {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(ppg_record_rows, dim3((unsigned)K.batch), dim3(64), 0, (hipStream_t)stream, K);
+    PPG_HIP_TRY(h, hipGetLastError());
+    return PPG_OK;
+}
+
 // ---- ppg_backward: returns and GAE over a recorded horizon (ppg_backward.h) ---------------------------------------
 extern "C" __global__ void __launch_bounds__(64) ppg_backward_rows(const ppg::BackwardParams K) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[ppg::BACKWARD_LDS_BYTES];

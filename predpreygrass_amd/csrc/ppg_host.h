@@ -20,6 +20,7 @@
 #include "ppg_pack.h"
 #include "ppg_fetch.h"
 #include "ppg_link.h"
+#include "ppg_record.h"
 #include "ppg_backward.h"
 
 // How a handle's step is scheduled (never what it computes): wavefronts per workgroup, the row count from which helper wavefronts
@@ -537,6 +538,17 @@ static int backend_link(ppg_handle *h, const ppg::LinkParams &K, void *stream);
 static void ppg_link_entry(void *arg) { ppg::link_main(*(const ppg::LinkParams *)arg, wv::emu().lds); }
 static int backend_link(ppg_handle *, const ppg::LinkParams &K, void *) {
     for (int b = 0; b < K.batch; ++b) wv::run_block(ppg_link_entry, (void *)&K, b, ppg::LINK_LDS_BYTES, 1);
+    return PPG_OK;
+}
+#endif
+// the launch of ppg_record (ppg_record.h)
+#ifndef PPG_WAVE_EMU
+static int backend_record(ppg_handle *h, const ppg::RecordParams &K, void *stream);
+#else
+// (CPU test build: defined here for the same reason as backend_link)
+static void ppg_record_entry(void *arg) { ppg::record_main(*(const ppg::RecordParams *)arg, wv::emu().lds); }
+static int backend_record(ppg_handle *, const ppg::RecordParams &K, void *) {
+    for (int b = 0; b < K.batch; ++b) wv::run_block(ppg_record_entry, (void *)&K, b, ppg::LINK_LDS_BYTES, 1);
     return PPG_OK;
 }
 #endif
@@ -1112,22 +1124,58 @@ int ppg_fetch(ppg_handle *h, int32_t env0, int32_t n_envs, void *host, uint64_t 
     return PPG_OK;
 }
 
-int ppg_link(ppg_handle *h, int16_t *prev_row, int16_t *next_row, void *stream) {
-    if (!h) return PPG_EINVAL;
+// the parameter block of a link launch (ppg_link, ppg_record); allocates the snapshot on first use
+static int ppg_link_params(ppg_handle *h, ppg::LinkParams &K, int16_t *prev_row, int16_t *next_row) {
     const size_t B = (size_t)h->batch, S = (size_t)h->base.S;
     if (!h->link_dev) {
         const int rc = backend_alloc(h, (void **)&h->link_dev, (B * S + B + 2 * B) * sizeof(int32_t));
         if (rc != PPG_OK) return rc;
         h->link_valid = 0;   // nothing in it yet: this call writes -1 everywhere and takes the first snapshot
     }
-    ppg::LinkParams K;
-    memset(&K, 0, sizeof K);
     K.batch = h->batch; K.S = h->base.S; K.cap_pred = h->base.cap_pred; K.cap_prey = h->base.cap_prey;
     K.valid = h->link_valid;
     K.row_id = h->bufs.row_id; K.row_flags = h->bufs.row_flags; K.env_state = h->bufs.env_state;
     K.snap_id = h->link_dev; K.snap_episode = h->link_dev + B * S; K.snap_rows = h->link_dev + B * S + B;
     K.prev_row = prev_row; K.next_row = next_row;
-    const int rc = backend_link(h, K, stream);
+    return PPG_OK;
+}
+
+int ppg_link(ppg_handle *h, int16_t *prev_row, int16_t *next_row, void *stream) {
+    if (!h) return PPG_EINVAL;
+    ppg::LinkParams K;
+    memset(&K, 0, sizeof K);
+    int rc = ppg_link_params(h, K, prev_row, next_row);
+    if (rc != PPG_OK) return rc;
+    rc = backend_link(h, K, stream);
+    if (rc == PPG_OK) h->link_valid = 1;
+    return rc;
+}
+
+int ppg_record(ppg_handle *h, const ppg_record_buffers *buf, uint64_t step, uint32_t flags, int16_t *prev_row, int16_t *next_row,
+               void *stream) {
+    if (!h) return PPG_EINVAL;
+    if (!buf) return ppg_fail(h, PPG_EINVAL, "ppg_record: buf is NULL");
+    if (!buf->reward || !buf->in_use || !buf->terminated || !buf->truncated || !buf->next_row)
+        return ppg_fail(h, PPG_EINVAL, "ppg_record: a buffer of ppg_record_buffers is NULL");
+    if (buf->horizon < 1) return ppg_fail(h, PPG_EINVAL, "ppg_record: horizon %d < 1", buf->horizon);
+    if (flags & ~PPG_RECORD_STEP_ON_DEVICE) return ppg_fail(h, PPG_EINVAL, "ppg_record: unknown flag bits 0x%x", flags);
+    const bool on_device = (flags & PPG_RECORD_STEP_ON_DEVICE) != 0;
+    if (on_device && !step) return ppg_fail(h, PPG_EINVAL, "ppg_record: PPG_RECORD_STEP_ON_DEVICE with a NULL address");
+    if (!on_device && step >= (uint64_t)buf->horizon)
+        return ppg_fail(h, PPG_EINVAL, "ppg_record: step %llu outside [0, %d)", (unsigned long long)step, buf->horizon);
+    const int S = h->base.S;
+    if (S % 64 != 0 || S < 64 || S > ppg::LINK_MAX_ROWS)   // the kernel's row registers: S / 64 per lane
+        return ppg_fail(h, PPG_EINVAL, "ppg_record: %d rows per env (needs a multiple of 64 up to %d)", S, ppg::LINK_MAX_ROWS);
+    ppg::RecordParams K;
+    memset((void *)&K, 0, sizeof K);
+    int rc = ppg_link_params(h, K, prev_row, next_row);
+    if (rc != PPG_OK) return rc;
+    K.T = buf->horizon; K.step_on_device = on_device;
+    K.step = on_device ? 0 : (int32_t)step;
+    K.step_dev = on_device ? (const int32_t *)(uintptr_t)step : nullptr;
+    K.row_reward = (const uint64_t *)h->bufs.row_reward; K.reward = (uint64_t *)buf->reward;
+    K.in_use = buf->in_use; K.terminated = buf->terminated; K.truncated = buf->truncated; K.traj_next = buf->next_row;
+    rc = backend_record(h, K, stream);
     if (rc == PPG_OK) h->link_valid = 1;
     return rc;
 }

@@ -99,11 +99,13 @@ PPG_DEVICE void link_species_n(const KP &K, int nr, size_t row0, int base, int n
     else if (nr == 4) link_species<4>(K, row0, base, n_cur, n_old, ids, nxt, ln);
 }
 
+// rows in use of env b in the call that was linked: what link_env read from env_state, for kernels that go on from it (ppg_record.h)
+struct LinkRows { int n_pred, n_prey; };
+
+// The link of ONE env by its wavefront (ppg_link_rows, and the first half of ppg_record_rows).  On return next[] of both species is
+// still in LDS at lds + LINK_MAX_ROWS * 4, int16 [S] in absolute rows, ordered behind a wv::sync().
 template <class KP>
-PPG_DEVICE void link_main(const KP &K, unsigned char *lds) {
-    const int b = PPG_BLOCK_INDEX();
-    if (b >= K.batch) return;
-    const int ln = wv::lane();
+PPG_DEVICE LinkRows link_env(const KP &K, unsigned char *lds, int b, int ln) {
     const int32_t *es = K.env_state + (size_t)b * PPG_ENV_WORDS;
     const int episode = es[PPG_ENV_EPISODE];
     const int np = link_clamp(es[PPG_ENV_N_PRED_ROWS], K.cap_pred), nq = link_clamp(es[PPG_ENV_N_PREY_ROWS], K.cap_prey);
@@ -122,6 +124,14 @@ PPG_DEVICE void link_main(const KP &K, unsigned char *lds) {
         K.snap_rows[2 * b] = np;
         K.snap_rows[2 * b + 1] = nq;
     }
+    return LinkRows{np, nq};
+}
+
+template <class KP>
+PPG_DEVICE void link_main(const KP &K, unsigned char *lds) {
+    const int b = PPG_BLOCK_INDEX();
+    if (b >= K.batch) return;
+    link_env(K, lds, b, wv::lane());
 }
 
 }  // namespace ppg

@@ -9,7 +9,7 @@ one kernel launch (`env.backward()`, `ppg_backward`).
     traj = AgentTrajectories(env, horizon=T)
     for t in range(T):
         env.step(actions)            # or random_actions=True, with or without auto_reset
-        traj.record()                # after EVERY step: link() compares with the output the previous record() saw
+        traj.record()                # after EVERY step: the link compares with the output the previous record() saw
     G = traj.returns(0.99)           # float64 [T,B,S]; G[t, b, r] belongs to the agent in row r of call t
     A = traj.gae(values, 0.99, 0.95)
     G, A = traj.returns_and_gae(values, 0.99, 0.95)   # both in ONE launch
@@ -25,9 +25,20 @@ so the horizon's last step is treated like an episode end; record one step more 
 The recursions run in the `ppg_backward` kernel (csrc/ppg_backward.h: one wavefront per env, step t + 1 in LDS): as a torch loop
 over the horizon -- about ten small launches per step, kept verbatim as `returns_torch()` / `gae_torch()` -- GAE over 128 steps of
 4096 envs took 20.8 ms, twice the rollout it post-processes, against 0.56 ms (profiles/EXPERIMENTS.md, `ppg_backward`); both give the
-same bits.  Recording
-(`record()`) stays plain torch copies behind `ppg_link`.  Not for `SubBatchedPredPreyGrass` as a whole: give each sub-batch its own
-AgentTrajectories.
+same bits.
+Recording (`record()`) is one launch too: `env.record()` (`ppg_record`, csrc/ppg_record.h) is the link kernel followed by the stores
+of the step.  As torch ops behind `ppg_link` -- about nineteen small launches, kept verbatim as `record_torch()` -- a recorded step of
+4096 envs took 162.2 µs launch to launch, with the kernel 115.5 µs, where the step alone takes 99.6 µs and step + `link()` 113.5 µs
+(profiles/EXPERIMENTS.md, `ppg_record`); both give the same bytes.
+
+    traj = AgentTrajectories(env, horizon=T, step_on_device=True)   # the step index is an int32 device tensor, `traj.t_dev`
+    loop = GraphedCollector(env, traj)                              # actions + step + record captured ONCE as a HIP graph
+    loop.replay(T - 1)                                              # (the uncaptured warm pass was step 0); no host work per step
+
+With `step_on_device` the kernel reads the step index when it runs and an increment follows it on the same stream, so nothing in
+the launch depends on a host value and a recorded step can be replayed; `len(traj)` and the backward methods read the index back
+once.  A record past the horizon then stores nothing (it still links) instead of raising.  Not for `SubBatchedPredPreyGrass` as a
+whole: give each sub-batch its own AgentTrajectories.
 """
 from __future__ import annotations
 
@@ -37,7 +48,7 @@ from . import _abi
 
 
 class AgentTrajectories:
-    def __init__(self, env, horizon):
+    def __init__(self, env, horizon, step_on_device=False):
         self.env = env
         self.horizon = int(horizon)
         if self.horizon < 1:
@@ -49,11 +60,33 @@ class AgentTrajectories:
         self.truncated = torch.zeros((T, B, S), dtype=torch.bool, device=dev)
         self.next_row = torch.full((T, B, S), -1, dtype=torch.int16, device=dev)
         self._slot = torch.arange(S, device=dev, dtype=torch.int32).unsqueeze(0)
-        self.t = 0
+        # step_on_device: the step index lives in `t_dev` (int32 [1] on the device), read by the record kernel when it runs and
+        # counted up behind it on the same stream -- no host value in the launch, so step + record can be captured and replayed
+        # (GraphedCollector).  A record() past the horizon then writes nothing (and still links) instead of raising.
+        self.step_on_device = bool(step_on_device)
+        self.t_dev = torch.zeros((1,), dtype=torch.int32, device=dev) if self.step_on_device else None
+        self._t = 0
+
+    @property
+    def t(self):
+        """Steps recorded so far.  With step_on_device: one read-back of t_dev, clamped to [0, horizon]."""
+        if self.step_on_device:
+            return min(max(int(self.t_dev.item()), 0), self.horizon)
+        return self._t
+
+    @t.setter
+    def t(self, value):
+        if self.step_on_device:
+            self.t_dev.fill_(int(value))
+        else:
+            self._t = int(value)
 
     def clear(self):
         """Start a new trajectory in the same tensors (the next record() is step 0 and links to nothing before it)."""
-        self.t = 0
+        if self.step_on_device:
+            self.t_dev.zero_()
+        else:
+            self._t = 0
         return self
 
     def __len__(self):
@@ -61,7 +94,24 @@ class AgentTrajectories:
 
     def record(self):
         """Store the output of the env's last call as step t.  Call it after every env.step of the trajectory, on the stream the
-        step ran on (torch's current stream: the link kernel and the copies below are enqueued there)."""
+        step ran on (torch's current stream).  ONE launch: `env.record()` (`ppg_record`: the link kernel plus the stores;
+        record_torch() is the same as torch ops).  With step_on_device the launch reads t_dev and an increment of it follows on the
+        same stream; past the horizon such a call stores nothing."""
+        env = self.env
+        if self.step_on_device:
+            env.record(self.reward, self.in_use, self.terminated, self.truncated, self.next_row, self.t_dev)
+            self.t_dev.add_(1)
+            return self
+        if self._t >= self.horizon:
+            raise RuntimeError(f"the trajectory is full ({self.horizon} steps): clear() it")
+        env.record(self.reward, self.in_use, self.terminated, self.truncated, self.next_row, self._t)
+        self._t += 1
+        return self
+
+    def record_torch(self):
+        """record() as torch ops behind `env.link()`: the same bytes, about nineteen small launches (timing baseline, fallback)."""
+        if self.step_on_device:
+            raise RuntimeError("record_torch() needs the step index on the host: AgentTrajectories(..., step_on_device=False)")
         if self.t >= self.horizon:
             raise RuntimeError(f"the trajectory is full ({self.horizon} steps): clear() it")
         env, t = self.env, self.t
@@ -89,7 +139,7 @@ class AgentTrajectories:
 
     def _backward(self, values, gamma, lam, returns):
         """The first len(self) steps of the stored tensors (a contiguous prefix) through env.backward()."""
-        n = self.t
+        n = self.t   # (step_on_device: the one read-back)
         B, S = self.reward.shape[1:]
         if values is not None:
             if tuple(values.shape) != (n, B, S):
@@ -149,3 +199,60 @@ class AgentTrajectories:
             a_next = torch.where(self.in_use[t], a, zero)
             A[t] = a_next
         return A
+
+
+class GraphedCollector:
+    """One recorded step -- actions, `ppg_step`, `ppg_record` and the increment of the step index -- captured ONCE into a HIP graph
+    and replayed: the capture protocol of policy.GraphedPolicyStep for a rollout that is recorded.  No host work per step.
+
+        traj = AgentTrajectories(env, horizon=T, step_on_device=True)
+        loop = GraphedCollector(env, traj)          # records step 0 (the uncaptured warm pass), then captures
+        loop.replay(T - 1)                          # steps 1 .. T-1
+        G = traj.returns(0.99)
+
+    act: a callable that enqueues whatever fills `env.actions` on the current stream -- e.g. ``fused.act(env, sample=True,
+    seed=seed_tensor)`` plus the increment of the seed tensor; without it the step draws uniform random actions on the device.
+    The body (act, step, record) runs once uncaptured on a side stream -- that pass IS a recorded step, step 0 of an empty `traj`; it
+    also creates the env's link tensors and leaves the link snapshot valid -- and is then captured as one linear chain on one stream.
+    Replays past the horizon keep stepping and linking and store nothing (`ppg_record`: a step index outside [0, T) writes no
+    buffer); `len(traj)` stays at T.
+
+    Limit: whether the link snapshot may be linked to (the library's host flag, cleared by reset / set_placement / import_state) is
+    baked into the graph when it is captured -- as "valid".  After `env.reset()`, `env.set_placement()` or `env.import_state()` run
+
+        traj.clear(); env.step(...); traj.record()      # eager: this record links nothing and takes the fresh snapshot
+
+    before the next replay(); a replay right after a reset would link the new rows to the old episode's snapshot."""
+
+    def __init__(self, env, traj, act=None, auto_reset=True):
+        if not getattr(traj, "step_on_device", False):
+            raise ValueError("GraphedCollector needs AgentTrajectories(..., step_on_device=True)")
+        if traj.env is not env:
+            raise ValueError("traj records another env")
+        if env.device.type != "cuda":
+            raise RuntimeError("GraphedCollector captures a HIP graph: the env must be on a GPU")
+        self.env, self.traj = env, traj
+        dev = env.device
+
+        def body():
+            if act is not None:
+                act()
+                env.step(env.actions, auto_reset=auto_reset)
+            else:
+                env.step(random_actions=True, auto_reset=auto_reset)
+            traj.record()
+        # (one uncaptured pass on a side stream first: lazy allocations of the library and of the env must not fall into the capture)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            body()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            body()
+
+    def replay(self, n: int = 1):
+        for _ in range(n):
+            self.graph.replay()
+        return self
