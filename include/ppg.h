@@ -372,6 +372,18 @@ int ppg_walls_changed(ppg_handle *h, void *stream);
  * every few dozen steps is enough (bench.py: every 64).  The order is used by every later launch of the handle. */
 int ppg_rebalance(ppg_handle *h, void *stream);
 
+/* Cache policy only, results are unaffected (the same bits): the cooperative step kernels write the observation rows of envs with
+ * index >= n with non-temporal stores, which do not displace what is resident in the 256 MiB Infinity Cache, so that the rows of envs
+ * 0 .. n-1 -- always the same addresses -- are rewritten in place there from step to step instead of going to HBM.  ppg_rebalance
+ * computes n on the device: the largest count of leading envs whose rows in use fit budget * batch / envs in flight
+ * (ppg_set_envs_in_flight; budget: 160 MiB, environment variable PPG_RESIDENT_BYTES read at ppg_create, 0 = off -- ppg_rebalance
+ * then leaves the word alone).  A handle that was never rebalanced, or whose envs in flight all fit, writes every row with plain
+ * stores.  ppg_set_resident_envs writes n directly (tests, A/B runs; it waits for the stream) until the next ppg_rebalance;
+ * ppg_get_resident_envs reads it back (batch if it was never written; waits for the stream).  ppg_rollout's fused kernels, the
+ * walls variant and the one-env-per-workgroup kernels ignore it. */
+int ppg_set_resident_envs(ppg_handle *h, int32_t n, void *stream);
+int ppg_get_resident_envs(ppg_handle *h, int32_t *n, void *stream);
+
 /* grid_world_state (BASE:124): dense float64 [B,4,G,G] rebuilt from the rows. */
 int ppg_export_grid(ppg_handle *h, double *grid_out, void *stream);
 

@@ -169,7 +169,7 @@ SPREAD_SYMBOLS = ["ppg_alloc_spread", "ppg_free_spread", "ppg_spread_stats", "pp
 EXPORTED_SYMBOLS = [
     "ppg_abi_version", "ppg_create", "ppg_destroy", "ppg_get_buffers", "ppg_reset", "ppg_reset_from_state", "ppg_observe", "ppg_step", "ppg_step_many",
     "ppg_rollout", "ppg_step_ordered", "ppg_create_gen2", "ppg_step_uniforms", "ppg_set_envs_in_flight", "ppg_set_wave_plan",
-    "ppg_get_wave_plan", "ppg_rebalance",
+    "ppg_get_wave_plan", "ppg_rebalance", "ppg_set_resident_envs", "ppg_get_resident_envs",
     "ppg_export_grid", "ppg_walls_changed", "ppg_state_bytes", "ppg_export_state", "ppg_import_state", "ppg_pack_bytes", "ppg_pack",
     "ppg_fetch_bytes", "ppg_fetch", "ppg_link", "ppg_record", "ppg_backward",
     "ppg_lexkey", "ppg_lds_bytes", "ppg_step_kernel_name", "ppg_last_error",
@@ -203,6 +203,11 @@ def bind(lib: C.CDLL) -> C.CDLL:
     lib.ppg_step_uniforms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
     lib.ppg_rebalance.restype = C.c_int
     lib.ppg_rebalance.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "ppg_set_resident_envs"):   # (absent from an older build loaded through PPG_HIP_LIB for an A/B run)
+        lib.ppg_set_resident_envs.restype = C.c_int
+        lib.ppg_set_resident_envs.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        lib.ppg_get_resident_envs.restype = C.c_int
+        lib.ppg_get_resident_envs.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
     lib.ppg_get_buffers.restype = C.c_int
     lib.ppg_get_buffers.argtypes = [C.c_void_p, C.c_void_p]
     lib.ppg_set_envs_in_flight.restype = C.c_int

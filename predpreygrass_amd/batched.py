@@ -313,6 +313,19 @@ class BatchedPredPreyGrass:
         self._check(self._lib.ppg_rebalance(self._handle, self._stream(stream)), "ppg_rebalance")
         return self
 
+    def set_resident_envs(self, n: int, stream=None):
+        """Cache policy only (results are unaffected): the cooperative step kernels write the observation rows of envs with index
+        >= n with non-temporal stores, so that the rows of envs 0 .. n-1 stay in the Infinity Cache from step to step
+        (`ppg_set_resident_envs`; `rebalance()` computes n itself unless PPG_RESIDENT_BYTES=0)."""
+        self._check(self._lib.ppg_set_resident_envs(self._handle, int(n), self._stream(stream)), "ppg_set_resident_envs")
+        return self
+
+    def resident_envs(self, stream=None) -> int:
+        """The count the step kernels use (`ppg_get_resident_envs`): the batch size until `rebalance()` or `set_resident_envs()` wrote one."""
+        n = C.c_int32(0)
+        self._check(self._lib.ppg_get_resident_envs(self._handle, C.byref(n), self._stream(stream)), "ppg_get_resident_envs")
+        return int(n.value)
+
     def observe(self):
         """Recompute the observations of all live rows from the current state tensors."""
         self._check(self._lib.ppg_observe(self._handle, self._stream()), "ppg_observe")

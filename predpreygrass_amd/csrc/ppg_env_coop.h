@@ -67,6 +67,8 @@
         // per call -- a loop of its own for float64 rows: 64x64 grids 54.6-55.6 -> 52.7-53.3 us per 4096-env step.  The four-map kernels
         // keep the one generic loop: there the second copy cost the headline 0.5-2 % (code size) -- profiles/r06/o_*.
         void *const obuf = type ? P.obs_prey : P.obs_pred;
+        // the env's store flavour (wave-uniform; a branch at each store, not a second copy of the loops: KParams::resident_envs)
+        const bool stream = !FUSED && eb >= n_resident;
         // The second generation's kernels do the same for float32 rows, the reference's dtype there (RQ:137-139): its branch chain is the
         // longest of the three -- 57.5 -> 53.5 us per 4096-env step, +7 % (profiles/r06/r_*).
         auto pieces = [&](auto f64_tag, auto f32_tag) {
@@ -99,7 +101,7 @@
                 for (int u = 0; u < U; ++u) {
                     float4 f;
                     f.x = (float)vt[ix[u][0]]; f.y = (float)vt[ix[u][1]]; f.z = (float)vt[ix[u][2]]; f.w = (float)vt[ix[u][3]];
-                    if (on[u]) *(float4 *)((float *)obuf + obase + o[u]) = f;
+                    if (on[u]) PPG_OBS_STORE(stream, (float4 *)((float *)obuf + obase + o[u]), f);
                 }
             }
             return;
@@ -127,9 +129,9 @@
                 for (int u = 0; u < U; ++u) {
                     const double v0 = vt[i0[u]], v1 = vt[i1[u]];
                     if (!on[u]) continue;
-                    if (F64) { double2 g; g.x = v0; g.y = v1; *(double2 *)((double *)obuf + obase + o[u]) = g; }
-                    else if (F32) { float2 f; f.x = (float)v0; f.y = (float)v1; *(float2 *)((float *)obuf + obase + o[u]) = f; }
-                    else store_obs_pair(obuf, P.obs_f32, obase + o[u], v0, v1);
+                    if (F64) { double2 g; g.x = v0; g.y = v1; PPG_OBS_STORE(stream, (double2 *)((double *)obuf + obase + o[u]), g); }
+                    else if (F32) { float2 f; f.x = (float)v0; f.y = (float)v1; PPG_OBS_STORE(stream, (float2 *)((float *)obuf + obase + o[u]), f); }
+                    else store_obs_pair(obuf, P.obs_f32, obase + o[u], v0, v1, stream);
                 }
             }
             return;
@@ -166,9 +168,9 @@
                 const double t0 = vt[i0[u]], t1 = vt[i1[u]];   // (channel 0 inside the grid: entry 0 = 0.0)
                 const double v0 = out0[u] ? 1.0 : t0, v1 = out1[u] ? 1.0 : t1;
                 if (!on[u]) continue;
-                if (F64) { double2 g; g.x = v0; g.y = v1; *(double2 *)((double *)obuf + obase + o[u]) = g; }
-                else if (F32) { float2 f; f.x = (float)v0; f.y = (float)v1; *(float2 *)((float *)obuf + obase + o[u]) = f; }
-                else store_obs_pair(obuf, P.obs_f32, obase + o[u], v0, v1);
+                if (F64) { double2 g; g.x = v0; g.y = v1; PPG_OBS_STORE(stream, (double2 *)((double *)obuf + obase + o[u]), g); }
+                else if (F32) { float2 f; f.x = (float)v0; f.y = (float)v1; PPG_OBS_STORE(stream, (float2 *)((float *)obuf + obase + o[u]), f); }
+                else store_obs_pair(obuf, P.obs_f32, obase + o[u], v0, v1, stream);
             }
         }
         };

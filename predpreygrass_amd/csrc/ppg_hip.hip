@@ -163,8 +163,13 @@ static void backend_free(ppg_handle *, void *p) { (void)hipFree(p); }
 // batch size.  Keys are small (<= 64 * 8 + 256 * 8), so the histogram lives in LDS; envs with equal keys land in arbitrary order
 // (atomics) -- the order only decides which workgroup steps which env, never a result.
 #define PPG_RANK_BINS 2568
-extern "C" __global__ void __launch_bounds__(1024) ppg_rank_envs(const int32_t *env_state, int batch, int wp, int wq, int32_t *order) {
+// resident != NULL: also *resident = the largest count of leading envs (env-index order) whose observation bytes, n_pred_rows * bytes_p
+// + n_prey_rows * bytes_q each, fit `share` (KParams::resident_envs; ppg_rebalance) -- a block-wide scan over contiguous runs of envs.
+extern "C" __global__ void __launch_bounds__(1024) ppg_rank_envs(const int32_t *env_state, int batch, int wp, int wq, int32_t *order,
+                                                                 int32_t *resident, long long share, int bytes_p, int bytes_q) {
     __shared__ int32_t hist[PPG_RANK_BINS];
+    __shared__ long long run_sum[1024];
+    __shared__ int32_t n_fit;
     const int t = (int)threadIdx.x;
     for (int k = t; k < PPG_RANK_BINS; k += 1024) hist[k] = 0;
     __syncthreads();
@@ -189,6 +194,29 @@ extern "C" __global__ void __launch_bounds__(1024) ppg_rank_envs(const int32_t *
         key = key < 0 ? 0 : (key >= PPG_RANK_BINS ? PPG_RANK_BINS - 1 : key);
         order[atomicAdd(&hist[key], 1)] = i;
     }
+    if (!resident) return;   // (uniform: a kernel argument)
+    const int per = (batch + 1023) / 1024, lo = t * per, hi = lo + per < batch ? lo + per : batch;   // this thread's run of envs
+    auto env_bytes = [&](int i) {
+        const int np = env_state[(size_t)i * PPG_ENV_WORDS + PPG_ENV_N_PRED_ROWS], nq = env_state[(size_t)i * PPG_ENV_WORDS + PPG_ENV_N_PREY_ROWS];
+        return (long long)(np > 0 ? np : 0) * bytes_p + (long long)(nq > 0 ? nq : 0) * bytes_q;
+    };
+    long long mine = 0;
+    for (int i = lo; i < hi; ++i) mine += env_bytes(i);
+    run_sum[t] = mine;
+    if (t == 0) n_fit = 0;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {   // inclusive scan of the 1024 run sums
+        const long long add = t >= d ? run_sum[t - d] : 0;
+        __syncthreads();
+        run_sum[t] += add;
+        __syncthreads();
+    }
+    long long acc = run_sum[t] - mine;   // bytes of the envs in front of this run
+    int fit = 0;
+    for (int i = lo; i < hi; ++i) { acc += env_bytes(i); fit += acc <= share; }   // (sums never decrease: the envs that fit are a prefix)
+    if (fit) atomicAdd(&n_fit, fit);
+    __syncthreads();
+    if (t == 0) *resident = n_fit;
 }
 
 static int backend_rebalance(ppg_handle *h, int weight_pred, int weight_prey, void *stream) {
@@ -196,7 +224,9 @@ static int backend_rebalance(ppg_handle *h, int weight_pred, int weight_prey, vo
     if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
     if (!h->order_dev) PPG_HIP_TRY(h, hipMalloc((void **)&h->order_dev, (size_t)h->batch * sizeof(int32_t)));
     hipLaunchKernelGGL(ppg_rank_envs, dim3(1), dim3(1024), 0, (hipStream_t)stream,
-                       (const int32_t *)h->bufs.env_state, (int)h->batch, weight_pred, weight_prey, h->order_dev);
+                       (const int32_t *)h->bufs.env_state, (int)h->batch, weight_pred, weight_prey, h->order_dev,
+                       h->resident_share >= 0 ? h->resident_dev : (int32_t *)nullptr, (long long)h->resident_share,
+                       (int)h->resident_row_bytes[0], (int)h->resident_row_bytes[1]);
     PPG_HIP_TRY(h, hipGetLastError());
     return PPG_OK;
 }

@@ -43,6 +43,11 @@ struct ppg_handle {
     int32_t coop_wgs_per_cu;  // float64 / float32 rows: four-wave cooperative workgroups a CU takes at most (PPG_COOP_WGS_PER_CU, read at create)
     int32_t step_lds_pad;     // experiment (PPG_STEP_LDS_PAD, read at create): unused LDS added to the multi-wave kernels' launches
     int32_t *order_dev;      // library-owned [batch]: env order of ppg_rebalance (NULL until first used)
+    int32_t *resident_dev;   // library-owned word: KParams::resident_envs (allocated at create; the kernels see it once it has been written)
+    int32_t resident_host;   // staging word of ppg_set_resident_envs / ppg_get_resident_envs
+    int64_t resident_bytes;  // observation bytes of the envs in flight that may stay in the Infinity Cache (PPG_RESIDENT_BYTES, read at create; 0 = off)
+    int64_t resident_share;  // ppg_rebalance -> backend_rebalance: this handle's share of resident_bytes (< 0: leave the word alone) ...
+    int32_t resident_row_bytes[2];   // ... and the bytes of one predator / prey observation row
     uint32_t *vis_dev;       // library-owned [batch, G*G, vis_words]: line-of-sight masks of the walls variant (ppg_walls_changed)
     unsigned char *fetch_dev;   // library-owned staging buffer of ppg_fetch (NULL until first used)
     uint64_t fetch_cap;         // its size
@@ -65,6 +70,13 @@ struct ppg_handle {
     char kernel_name[48];          // ppg_step_kernel_name
     char err[256];
 };
+
+// Bytes of observations that stay resident in the 256 MiB Infinity Cache from step to step (ppg_rebalance: the leading envs whose
+// rows fit; the other envs' rows are written with non-temporal stores, which do not displace them).  160 MiB: the fastest split of the
+// bare write pattern on two sets of pages, 59.0-59.2 us against 70.9-82.0 for plain stores, and the largest part that still runs at
+// the cache's speed on its own -- 192 MiB alone already drops from 38 to 49 us (tools/store_resident_split.hip; the table is in
+// profiles/EXPERIMENTS.md, resident split).  PPG_RESIDENT_BYTES overrides it at ppg_create; 0 = off.
+#define PPG_RESIDENT_BYTES_DEFAULT (160ll << 20)
 
 static char g_ppg_create_error[256] = "";
 
@@ -605,8 +617,12 @@ static int ppg_create_common(const ppg_config *cfg, const ppg_config_gen2 *cfg2,
         h->step_lds_pad = pad ? atoi(pad) : 0;
         const char *pf = getenv("PPG_BACKWARD_PREFETCH");   // (A/B of ppg_backward's load placement: profiles/EXPERIMENTS.md)
         h->backward_prefetch = pf ? (atoi(pf) != 0) : 1;
+        const char *rb = getenv("PPG_RESIDENT_BYTES");
+        h->resident_bytes = rb ? atoll(rb) : PPG_RESIDENT_BYTES_DEFAULT;
+        if (h->resident_bytes < 0) h->resident_bytes = 0;
     }
     h->order_dev = nullptr;
+    h->resident_dev = nullptr; h->resident_host = 0; h->resident_share = -1; h->resident_row_bytes[0] = h->resident_row_bytes[1] = 0;
     h->vis_dev = nullptr;
     h->fetch_dev = nullptr; h->fetch_cap = 0; h->fetch_hint = 0;
     h->link_dev = nullptr; h->link_valid = 0;
@@ -614,6 +630,7 @@ static int ppg_create_common(const ppg_config *cfg, const ppg_config_gen2 *cfg2,
     int rc = cfg2 ? ppg_validate_and_layout_gen2(h) : ppg_validate_and_layout(h);
     if (rc == PPG_OK) ppg_coop_layout(h);
     if (rc == PPG_OK) rc = backend_init(h, device);
+    if (rc == PPG_OK) rc = backend_alloc(h, (void **)&h->resident_dev, sizeof(int32_t));
     if (rc != PPG_OK) {
         memcpy(g_ppg_create_error, h->err, sizeof g_ppg_create_error);
         backend_release(h);
@@ -642,6 +659,8 @@ int ppg_destroy(ppg_handle *h) {
     if (!h) return PPG_OK;
     if (h->link_dev) backend_free(h, h->link_dev);
     h->link_dev = nullptr;
+    if (h->resident_dev) backend_free(h, h->resident_dev);
+    h->resident_dev = nullptr;
     backend_release(h);
     delete h;
     return PPG_OK;
@@ -749,6 +768,7 @@ static ppg::KParams ppg_planned_step_params(const ppg_handle *h, bool fused = fa
             }
         }
         P.env_order = h->base.env_order;
+        P.resident_envs = fused ? nullptr : h->base.resident_envs;   // (the fused kernels keep plain stores)
         P.vis_masks = h->base.vis_masks;
         P.vis_env_stride = h->base.vis_env_stride;
     }
@@ -820,11 +840,59 @@ int ppg_step_uniforms(ppg_handle *h, const int8_t *actions, const uint8_t *act_r
     return backend_launch(h, mode, P, stream);
 }
 
+static int ppg_pack_geometry(const ppg_handle *h, uint32_t flags, int &blk_p, int &blk_q, int &src_elem, int &dst_elem);
+
 int ppg_rebalance(ppg_handle *h, void *stream) {
     if (!h) return PPG_EINVAL;
     const ppg::KParams &P = h->base;
+    // the resident split (KParams::resident_envs): M = the largest count of leading envs -- in env-index order, not in rank order: the
+    // resident set has to be the same addresses from call to call -- whose observation rows fit this handle's share of the budget,
+    // resident_bytes * batch / envs in flight (sub-batches split one budget).  All envs in flight fit: M = batch, nothing streams.
+    h->resident_share = -1;
+    if (h->resident_bytes > 0 && h->resident_dev) {
+        int bp, bq, se, de;
+        ppg_pack_geometry(h, 0, bp, bq, se, de);
+        const int64_t in_flight = h->envs_in_flight > h->batch ? h->envs_in_flight : h->batch;
+        h->resident_share = (int64_t)((__int128)h->resident_bytes * h->batch / in_flight);
+        h->resident_row_bytes[0] = bp * se; h->resident_row_bytes[1] = bq * se;
+    }
     const int rc = backend_rebalance(h, P.nch_p, P.nch_q, stream);   // weight = 128-element chunks per observation
-    if (rc == PPG_OK) h->base.env_order = h->order_dev;
+    if (rc != PPG_OK) return rc;
+    h->base.env_order = h->order_dev;
+    if (h->resident_share >= 0) {
+#ifdef PPG_WAVE_EMU   // (the emulator's backend_rebalance only ranks: the same cut, computed here)
+        const int32_t *es = h->bufs.env_state;
+        int64_t acc = 0;
+        int m = 0;
+        for (; m < h->batch; ++m) {
+            const int32_t np = es[(size_t)m * PPG_ENV_WORDS + PPG_ENV_N_PRED_ROWS], nq = es[(size_t)m * PPG_ENV_WORDS + PPG_ENV_N_PREY_ROWS];
+            acc += (int64_t)(np > 0 ? np : 0) * h->resident_row_bytes[0] + (int64_t)(nq > 0 ? nq : 0) * h->resident_row_bytes[1];
+            if (acc > h->resident_share) break;
+        }
+        *h->resident_dev = m;
+#endif
+        h->base.resident_envs = h->resident_dev;
+    }
+    return PPG_OK;
+}
+
+int ppg_set_resident_envs(ppg_handle *h, int32_t n, void *stream) {
+    if (!h) return PPG_EINVAL;
+    if (n < 0) return ppg_fail(h, PPG_EINVAL, "ppg_set_resident_envs: n < 0");
+    h->resident_host = n;
+    int rc = backend_copy(h, h->resident_dev, &h->resident_host, sizeof(int32_t), true, stream);
+    if (rc == PPG_OK) rc = backend_sync(h, stream);   // (the staging word may change with the next call)
+    if (rc == PPG_OK) h->base.resident_envs = h->resident_dev;
+    return rc;
+}
+
+int ppg_get_resident_envs(ppg_handle *h, int32_t *n, void *stream) {
+    if (!h || !n) return PPG_EINVAL;
+    *n = h->batch;   // never written: every env is resident
+    if (!h->base.resident_envs) return PPG_OK;
+    int rc = backend_copy(h, &h->resident_host, h->resident_dev, sizeof(int32_t), false, stream);
+    if (rc == PPG_OK) rc = backend_sync(h, stream);
+    if (rc == PPG_OK) *n = h->resident_host;
     return rc;
 }
 

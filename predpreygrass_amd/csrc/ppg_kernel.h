@@ -172,6 +172,9 @@ struct KParams {
                                // map_n / 4 words, the padded channel-0 map of an empty grid (halo cells = Env::ONE_IDX).  ch0_map 0:
                                // channel 0 ("outside the grid", BASE:520-523) has no map: bits 16-31 = 0xFFFF, bits 4-7 (i - off) + 8,
                                // bits 0-3 (j - off) + 8 -- the element is 1.0 iff (x + i - off, y + j - off) lies outside the grid
+    const int32_t *resident_envs;  // library-owned word M (ppg_rebalance, ppg_set_resident_envs), cooperative step kernels: envs with index
+                               // >= M write their observations with non-temporal stores, so that the rows of envs 0 .. M-1 -- always the
+                               // same addresses -- stay in the Infinity Cache from step to step.  NULL: every env is resident (plain stores)
 };
 
 // ---------------------------------------------------------------------------------
@@ -238,17 +241,37 @@ PPG_DEVICE uint32_t bf16_bits(float f) {
     return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
 }
 
+// One observation store of a cooperative writer: `stream` (wave-uniform: the env is not one of KParams::resident_envs) makes it
+// non-temporal -- the same bytes, only the cache policy differs: such a store does not displace what is resident in the Infinity
+// Cache (profiles/EXPERIMENTS.md, resident split).  A plain store on the CPU emulator.
+#ifdef PPG_WAVE_EMU
+#define PPG_OBS_STORE(stream, ptr, value) (*(ptr) = (value))
+#else
+template <class T> PPG_DEVICE void obs_store(bool stream, T *p, const T &v) {
+    typedef uint32_t words_t __attribute__((ext_vector_type(sizeof(T) / 4)));
+    if (stream) {
+        // (the empty statements keep the two stores apart: left alone, the optimiser hoists or sinks the "common" store out of the
+        // branch and drops the non-temporal hint with it -- no `nt` store was left in any kernel)
+        asm volatile("");
+        __builtin_nontemporal_store(__builtin_bit_cast(words_t, v), (words_t *)p);
+        asm volatile("");
+    } else *p = v;
+}
+#define PPG_OBS_STORE(stream, ptr, value) obs_store((stream), (ptr), (value))
+#endif
+
 // elements o, o + 1 of an observation buffer (o even) as one vector store: float64 (the reference's dtype), float32, or bfloat16
 // (obs_dtype 2: the compact rows the policy kernels stage from -- SURVEY 8(f) N4)
-PPG_DEVICE void store_obs_pair(void *base, int obs_dtype, size_t o, double v0, double v1) {
+PPG_DEVICE void store_obs_pair(void *base, int obs_dtype, size_t o, double v0, double v1, bool stream = false) {
     if (obs_dtype == 1) {
         float2 f; f.x = (float)v0; f.y = (float)v1;
-        *(float2 *)((float *)base + o) = f;
+        PPG_OBS_STORE(stream, (float2 *)((float *)base + o), f);
     } else if (obs_dtype == 2) {
-        *(uint32_t *)((uint16_t *)base + o) = bf16_bits((float)v0) | (bf16_bits((float)v1) << 16);
+        const uint32_t u = bf16_bits((float)v0) | (bf16_bits((float)v1) << 16);
+        PPG_OBS_STORE(stream, (uint32_t *)((uint16_t *)base + o), u);
     } else {
         double2 g; g.x = v0; g.y = v1;
-        *(double2 *)((double *)base + o) = g;
+        PPG_OBS_STORE(stream, (double2 *)((double *)base + o), g);
     }
 }
 
@@ -346,6 +369,7 @@ struct Env {
     // COOP: the workgroup's shared LDS area (set by env_main): observation descriptors and control words
     uint32_t *lut2 = nullptr;
     uint32_t *ctl = nullptr;
+    int n_resident = 0x7FFFFFFF;  // COOP step kernels: KParams::resident_envs' word (coop_main); the fused kernels never set it
     // control words: per env slot k of the workgroup CTL_SLOT + 4k: live predator rows, live prey rows, env index (-1 = no env);
     // per wavefront w CTL_MID + w: the (row, cell) entry of a mid-step observation
     // CTL_READY: bit k = env slot k's transition is over, its rows are published; CTL_TICKET + 2k + species: the next piece of that
@@ -645,6 +669,7 @@ PPG_DEVICE void coop_main(const KParams &P, unsigned char *lds) {
     env.wave_idx = w;
     env.lut2 = lut2;
     env.ctl = ctl;
+    if (!WALLS && Pc->resident_envs) env.n_resident = (int)wv::first((uint32_t)*Pc->resident_envs);   // (the walls writers keep plain stores)
     // (every wavefront that steps an env writes the whole descriptor table, identical words: it may need it for a mid-step
     // observation long before the workgroup's barrier; a workgroup always has at least one env)
     if (CoopEnv::DYN) {   // READY bits and tickets start at zero (all wavefronts are still here: this barrier costs nothing)
