@@ -38,6 +38,21 @@ def agent_name(type_: int, id_: int) -> str:
     return ("predator_%d" if type_ == PREDATOR else "prey_%d") % int(id_)
 
 
+def _alloc_on(device, stream, fn):
+    """fn() -- an allocation, with its fill if it has one -- for a launch on `stream`.  A torch.cuda.Stream: under
+    `torch.cuda.stream(stream)`, so the fill runs on that stream and the caching allocator knows which stream uses the blocks.  A raw
+    hipStream_t handle is unknown to torch: on the current stream, which the host then waits for -- the fill has to be complete, and a
+    recycled block no longer in use there, before the launch runs.  No stream, or the CPU (emulated library): plainly."""
+    if device.type != "cuda" or stream is None:
+        return fn()
+    if hasattr(stream, "cuda_stream"):
+        with torch.cuda.stream(stream):
+            return fn()
+    out = fn()
+    torch.cuda.current_stream(device).synchronize()
+    return out
+
+
 class BatchedPredPreyGrass:
     """Tensor API.
 
@@ -56,14 +71,8 @@ class BatchedPredPreyGrass:
         (profiles/EXPERIMENTS.md, round 3; N = 32 costs a few seconds and N x the tensors' size of transient device memory).  They stay valid
         until close()."""
         cfg = resolve_config(config)
-        self.config = cfg
-        self._obs_spread = int(obs_spread)
-        self.batch_size = int(batch_size)
-        self._init_device(device, obs_dtype, _library)
-        self.grid_size = int(cfg["grid_size"])
-        self.Rp, self.Rq = int(cfg["predator_obs_range"]), int(cfg["prey_obs_range"])
+        self._init_common(cfg, batch_size, device, obs_dtype, _library, obs_spread)
         self.P0, self.Q0 = int(cfg["n_initial_active_predator"]), int(cfg["n_initial_active_prey"])
-        self.n_grass = int(cfg["initial_num_grass"])
         # drive-conditioned variant (drive_conditioned_environment/predpreygrass_rllib_env.py:54-89): extra observation
         # channels filled with per-agent scalars; absent / False = the base environment
         drive = bool(cfg.get("enable_drive_channels", False))
@@ -123,7 +132,11 @@ class BatchedPredPreyGrass:
         self.set_seeds(seed)
 
     # ------------------------------------------------------------------
-    def _init_device(self, device, obs_dtype, _library):
+    def _init_common(self, cfg, batch_size, device, obs_dtype, _library, obs_spread):
+        """What every family's __init__ starts with: the config, the library and its device, the geometry the buffers are sized from."""
+        self.config = cfg
+        self._obs_spread = int(obs_spread)
+        self.batch_size = int(batch_size)
         self._emulated = _library is not None
         self._link_rows = None   # (prev_row, next_row) of link(), allocated on first use
         if _library is None:
@@ -145,6 +158,9 @@ class BatchedPredPreyGrass:
         if obs_dtype not in (torch.float64, torch.float32, torch.bfloat16):
             raise ValueError("obs_dtype must be torch.float64, torch.float32 or torch.bfloat16")
         self.obs_dtype = obs_dtype
+        self.grid_size = int(cfg["grid_size"])
+        self.Rp, self.Rq = int(cfg["predator_obs_range"]), int(cfg["prey_obs_range"])
+        self.n_grass = int(cfg["initial_num_grass"])
 
     def _abi_obs_dtype(self):
         return {torch.float64: 0, torch.float32: 1, torch.bfloat16: 2}[self.obs_dtype]
@@ -178,10 +194,8 @@ class BatchedPredPreyGrass:
         self.env_seed = z((B,), torch.int64)
         self.grass_xy = z((B, NG), torch.int16)
         self.grass_energy = z((B, NG), torch.float64)
-        nc = getattr(self, "obs_channels", 4)
-        ncp, ncq = getattr(self, "obs_channels_pred", nc), getattr(self, "obs_channels_prey", nc)
-        self.obs_pred = self._obs_tensor((B, self.pred_capacity, ncp, self.Rp, self.Rp), seed_salt=1)
-        self.obs_prey = self._obs_tensor((B, self.prey_capacity, ncq, self.Rq, self.Rq), seed_salt=2)
+        self.obs_pred = self._obs_tensor((B, self.pred_capacity, self.obs_channels_pred, self.Rp, self.Rp), seed_salt=1)
+        self.obs_prey = self._obs_tensor((B, self.prey_capacity, self.obs_channels_prey, self.Rq, self.Rq), seed_salt=2)
         self.actions = torch.full((B, S), _abi.ACTION_NONE, dtype=torch.int8, device=dev)
 
     def _obs_tensor(self, shape, seed_salt=0):
@@ -249,6 +263,49 @@ class BatchedPredPreyGrass:
         if rc != 0:
             raise RuntimeError(f"{what} failed ({rc}): {self._lib.ppg_last_error(self._handle).decode()}")
 
+    def _tensor_arg(self, name, x, dtypes, shape):
+        """The pointer of a tensor argument of a launch; ValueError unless it is a contiguous tensor of one of `dtypes` and of `shape`
+        (None = any size in that dimension) on the env's device."""
+        got = tuple(x.shape)
+        if x.dtype not in dtypes or (got != shape and (len(got) != len(shape) or any(n not in (None, g) for n, g in zip(shape, got)))) \
+                or x.device != self.device or not x.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {' / '.join(str(d) for d in dtypes)} tensor "
+                             f"[{','.join('*' if n is None else str(n) for n in shape)}] on {self.device}, not a"
+                             f"{'' if x.is_contiguous() else ' non-contiguous'} {x.dtype} tensor {list(got)} on {x.device}")
+        return C.c_void_p(x.data_ptr())
+
+    def _step_args(self, actions, random_actions, auto_reset, act_rank=None, n_steps=None):
+        """(flags, actions pointer, rank pointer) of a step launch.  n_steps: of a rollout, whose action tape is [n_steps,B,S] and has
+        no default.  With random_actions no tensor is looked at."""
+        flags = (_abi.STEP_RANDOM_ACTIONS if random_actions else 0) | (_abi.STEP_AUTO_RESET if auto_reset else 0)
+        shape = (self.batch_size, self.S)
+        ptr = rank = None
+        if not random_actions:
+            if actions is None:
+                if n_steps is not None:
+                    raise ValueError("a rollout takes its actions from a tape int8 [n_steps,B,S] or from random_actions=True")
+                actions = self.actions
+            ptr = self._tensor_arg("actions", actions, (torch.int8,), shape if n_steps is None else (n_steps,) + shape)
+        if act_rank is not None:
+            if random_actions:
+                raise ValueError("act_rank cannot be combined with random_actions")
+            rank = self._tensor_arg("act_rank", act_rank, (torch.uint8,), shape)
+        return flags, ptr, rank
+
+    _TRAJECTORY_DTYPES = {"reward": (torch.float64,), "next_row": (torch.int16,), "in_use": (torch.bool, torch.uint8),
+                          "terminated": (torch.bool, torch.uint8), "truncated": (torch.bool, torch.uint8),
+                          "values": (torch.float64, torch.float32)}
+
+    def _trajectory_args(self, **tensors):
+        """The [T,B,S] tensors of record() / backward(), checked in the order given; `reward` sets T >= 1.  Returns (T,B,S)."""
+        reward = tensors["reward"]
+        if reward.dim() != 3 or reward.shape[0] < 1 or tuple(reward.shape[1:]) != (self.batch_size, self.S):
+            raise ValueError(f"reward must be [T,{self.batch_size},{self.S}] with T >= 1, not {tuple(reward.shape)}")
+        shape = tuple(reward.shape)
+        for name, x in tensors.items():
+            self._tensor_arg(name, x, self._TRAJECTORY_DTYPES[name], shape)
+        return shape
+
     # ------------------------------------------------------------------
     def set_seeds(self, seed):
         """Env b gets Philox key ``seed + b`` (or the given per-env array)."""
@@ -265,9 +322,8 @@ class BatchedPredPreyGrass:
         self._check(self._lib.ppg_reset(self._handle, None, int(episode), self._stream()), "ppg_reset")
         return self
 
-    def set_placement(self, pred_xy, prey_xy, grass_xy, episode=0):
-        """reset() with a given placement (arrays [B,P0,2], [B,Q0,2], [B,n_grass,2] of (x, y)):
-        writes the initial state (predpreygrass_rllib_env.py:138-212) and computes the observations."""
+    def _placement_arrays(self, pred_xy, prey_xy, grass_xy):
+        """set_placement's three arguments as int64 arrays [B,n,2]: every position inside the grid, an env's grass cells all different."""
         B, G = self.batch_size, self.grid_size
         pred = np.asarray(pred_xy, dtype=np.int64).reshape(B, self.P0, 2)
         prey = np.asarray(prey_xy, dtype=np.int64).reshape(B, self.Q0, 2)
@@ -279,9 +335,15 @@ class BatchedPredPreyGrass:
         for b in range(B):
             if len(np.unique(gcell[b])) != self.n_grass:
                 raise ValueError("grass positions must be unique")
+        return pred, prey, grass
+
+    def set_placement(self, pred_xy, prey_xy, grass_xy, episode=0):
+        """reset() with a given placement (arrays [B,P0,2], [B,Q0,2], [B,n_grass,2] of (x, y)):
+        writes the initial state (predpreygrass_rllib_env.py:138-212) and computes the observations."""
         # the tables are built by the library (`ppg_reset_from_state`: row tables, OWNS bits in id order, grass table, env words,
         # then one ppg_observe launch)
-        arrays = [np.ascontiguousarray((a[..., 0] << 8 | a[..., 1]).astype(np.uint16)) for a in (pred, prey, grass)]
+        arrays = [np.ascontiguousarray((a[..., 0] << 8 | a[..., 1]).astype(np.uint16))
+                  for a in self._placement_arrays(pred_xy, prey_xy, grass_xy)]
         init = _abi.PpgInitState()
         init.pred_xy, init.prey_xy, init.grass_xy = (a.ctypes.data for a in arrays)
         init.episode = int(episode)
@@ -337,27 +399,9 @@ class BatchedPredPreyGrass:
         act_rank (optional uint8 [B,S]): position of each acting row within its type's action
         sequence, for action dicts whose order differs from row order.
         stream (optional): launch on this torch.cuda.Stream instead of torch's current stream."""
-        flags = 0
-        ptr = None
-        if random_actions:
-            flags |= _abi.STEP_RANDOM_ACTIONS
-        else:
-            if actions is None:
-                actions = self.actions
-            if actions.dtype != torch.int8 or tuple(actions.shape) != (self.batch_size, self.S) or \
-                    actions.device != self.device or not actions.is_contiguous():
-                raise ValueError(f"actions must be a contiguous int8 tensor [{self.batch_size},{self.S}] on {self.device}")
-            ptr = C.c_void_p(actions.data_ptr())
-        if auto_reset:
-            flags |= _abi.STEP_AUTO_RESET
-        if act_rank is not None:
-            if random_actions:
-                raise ValueError("act_rank cannot be combined with random_actions")
-            if act_rank.dtype != torch.uint8 or tuple(act_rank.shape) != (self.batch_size, self.S) or \
-                    act_rank.device != self.device or not act_rank.is_contiguous():
-                raise ValueError("act_rank must be a contiguous uint8 tensor [B,S] on the env's device")
-            self._check(self._lib.ppg_step_ordered(self._handle, ptr, C.c_void_p(act_rank.data_ptr()), flags,
-                                                   self._stream(stream)), "ppg_step_ordered")
+        flags, ptr, rank = self._step_args(actions, random_actions, auto_reset, act_rank)
+        if rank is not None:
+            self._check(self._lib.ppg_step_ordered(self._handle, ptr, rank, flags, self._stream(stream)), "ppg_step_ordered")
         else:
             self._check(self._lib.ppg_step(self._handle, ptr, flags, self._stream(stream)), "ppg_step")
         return self
@@ -385,14 +429,11 @@ class BatchedPredPreyGrass:
     def rollout(self, n_steps, actions=None, random_actions=False, auto_reset=False, stream=None):
         """`n_steps` transitions in ONE kernel launch (state stays on chip between steps): the same result
         as `n_steps` calls of step().  Actions come from the device-side uniform random policy
-        (`random_actions=True`) or from an action tape `actions` int8 [n_steps, B, S]."""
-        flags = (_abi.STEP_RANDOM_ACTIONS if random_actions else 0) | (_abi.STEP_AUTO_RESET if auto_reset else 0)
-        ptr = None
-        if not random_actions:
-            if actions is None or actions.dtype != torch.int8 or tuple(actions.shape) != (n_steps, self.batch_size, self.S) \
-                    or actions.device != self.device or not actions.is_contiguous():
-                raise ValueError(f"actions must be a contiguous int8 tensor [{n_steps},{self.batch_size},{self.S}] on {self.device}")
-            ptr = C.c_void_p(actions.data_ptr())
+        (`random_actions=True`) or from an action tape `actions` int8 [n_steps, B, S].
+        Second generation: the fused form of the cooperative step kernel (the handle's wave plan must be cooperative with four waves --
+        the default on a full GPU, else `set_wave_plan(4, 0, 2)`; not for the walls variant); the reproduction uniforms come from the
+        device's Philox streams."""
+        flags, ptr, _ = self._step_args(actions, random_actions, auto_reset, n_steps=n_steps)
         self._check(self._lib.ppg_rollout(self._handle, int(n_steps), ptr, flags, self._stream(stream)), "ppg_rollout")
         return self
 
@@ -415,15 +456,8 @@ class BatchedPredPreyGrass:
     def _link_tensors(self, stream=None):
         """The env's (prev_row, next_row) of link() / record(), allocated on first use."""
         if self._link_rows is None:
-            def alloc():
-                return tuple(torch.full((self.batch_size, self.S), -1, dtype=torch.int16, device=self.device) for _ in range(2))
-            if self.device.type == "cuda" and hasattr(stream, "cuda_stream"):
-                with torch.cuda.stream(stream):
-                    self._link_rows = alloc()
-            else:
-                self._link_rows = alloc()
-                if self.device.type == "cuda" and stream is not None:   # a raw stream handle: the fill has to be complete before it runs
-                    torch.cuda.current_stream(self.device).synchronize()
+            self._link_rows = _alloc_on(self.device, stream, lambda: tuple(
+                torch.full((self.batch_size, self.S), -1, dtype=torch.int16, device=self.device) for _ in range(2)))
         return self._link_rows
 
     def record(self, reward, in_use, terminated, truncated, next_row, t, stream=None):
@@ -434,15 +468,7 @@ class BatchedPredPreyGrass:
         step + record can then be replayed while the graph counts the tensor up); if that word is outside [0, T) the call is
         link() and writes no buffer.  Returns link()'s (prev_row, next_row): the env's own tensors, written exactly as by link().
         stream (optional): as in link()."""
-        if reward.dim() != 3 or reward.shape[0] < 1 or tuple(reward.shape[1:]) != (self.batch_size, self.S):
-            raise ValueError(f"reward must be [T,{self.batch_size},{self.S}] with T >= 1, not {tuple(reward.shape)}")
-        shape = tuple(reward.shape)
-        flag = (torch.bool, torch.uint8)
-        for name, x, dtypes in (("reward", reward, (torch.float64,)), ("in_use", in_use, flag), ("terminated", terminated, flag),
-                                ("truncated", truncated, flag), ("next_row", next_row, (torch.int16,))):
-            if x.dtype not in dtypes or tuple(x.shape) != shape or x.device != self.device or not x.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous {' / '.join(str(d) for d in dtypes)} tensor {list(shape)} on "
-                                 f"{self.device}, not {x.dtype} {list(x.shape)} on {x.device}")
+        shape = self._trajectory_args(reward=reward, in_use=in_use, terminated=terminated, truncated=truncated, next_row=next_row)
         if isinstance(t, torch.Tensor):
             if t.dtype != torch.int32 or t.numel() != 1 or t.device != self.device:
                 raise ValueError(f"t must be an int or a one-element int32 tensor on {self.device}")
@@ -472,28 +498,10 @@ class BatchedPredPreyGrass:
             raise ValueError("backward: neither returns nor advantages asked for")
         if want_a and values is None:
             raise ValueError("backward: advantages need values")
-        if reward.dim() != 3 or reward.shape[0] < 1 or tuple(reward.shape[1:]) != (self.batch_size, self.S):
-            raise ValueError(f"reward must be [T,{self.batch_size},{self.S}] with T >= 1, not {tuple(reward.shape)}")
-        shape = tuple(reward.shape)
-        flag = (torch.bool, torch.uint8)
-        tensors = [("reward", reward, (torch.float64,)), ("next_row", next_row, (torch.int16,)), ("in_use", in_use, flag),
-                   ("terminated", terminated, flag), ("truncated", truncated, flag)]
-        if want_a:
-            tensors.append(("values", values, (torch.float64, torch.float32)))
-        for name, x, dtypes in tensors:
-            if x.dtype not in dtypes or tuple(x.shape) != shape or x.device != self.device or not x.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous {' / '.join(str(d) for d in dtypes)} tensor {list(shape)} on "
-                                 f"{self.device}, not {x.dtype} {list(x.shape)} on {x.device}")
-
-        def alloc():
-            return tuple(torch.empty(shape, dtype=torch.float64, device=self.device) if want else None for want in (returns, want_a))
-        if self.device.type == "cuda" and hasattr(stream, "cuda_stream"):
-            with torch.cuda.stream(stream):
-                G, A = alloc()
-        else:
-            G, A = alloc()
-            if self.device.type == "cuda" and stream is not None:   # a raw stream handle: the block may still be in use on torch's stream
-                torch.cuda.current_stream(self.device).synchronize()
+        shape = self._trajectory_args(reward=reward, next_row=next_row, in_use=in_use, terminated=terminated, truncated=truncated,
+                                      **({"values": values} if want_a else {}))
+        G, A = _alloc_on(self.device, stream, lambda: tuple(
+            torch.empty(shape, dtype=torch.float64, device=self.device) if want else None for want in (returns, want_a)))
 
         def ptr(x):
             return None if x is None else C.c_void_p(x.data_ptr())
@@ -533,14 +541,9 @@ class BatchedPredPreyGrass:
     def _fetch_fields(self):
         """(name, numpy dtype, elements) of an env's record in a fetch image: the state image's field order (include/ppg.h)."""
         S, NG = self.S, self.grass_capacity
-        f = [("row_xy", "<i2", S), ("row_energy", "<f8", S), ("row_id", "<i4", S), ("row_key", "<i4", S), ("row_cumrew", "<f8", S),
-             ("row_flags", "u1", S), ("row_reward", "<f8", S), ("row_parent", "<i4", S), ("env_state", "<i4", _abi.ENV_WORDS),
-             ("env_seed", "<i8", 1), ("grass_xy", "<i2", NG), ("grass_energy", "<f8", NG)]
-        if hasattr(self, "walls"):   # BatchedRedQueen (ppg_create_gen2)
-            f.append(("row_lastrep", "<i4", S))
-            if self.walls:
-                f += [("row_info", "u1", S), ("wall_bits", "<i4", int(self.wall_bits.shape[1]))]
-        return f
+        return [("row_xy", "<i2", S), ("row_energy", "<f8", S), ("row_id", "<i4", S), ("row_key", "<i4", S), ("row_cumrew", "<f8", S),
+                ("row_flags", "u1", S), ("row_reward", "<f8", S), ("row_parent", "<i4", S), ("env_state", "<i4", _abi.ENV_WORDS),
+                ("env_seed", "<i8", 1), ("grass_xy", "<i2", NG), ("grass_energy", "<f8", NG)]
 
     def _host_buffer(self, nbytes, dtype=torch.uint8):
         """Host memory the library copies into / out of: pinned on a GPU (the copy is then asynchronous), plain for the CPU test build."""
@@ -613,12 +616,13 @@ class BatchedPredPreyGrass:
 
     # ------------------------------------------------------------------
     # host views (one device->host copy each; used by tests and by white-box state surgery)
+    _HOST_TABLES = ("row_xy", "row_energy", "row_id", "row_cumrew", "row_flags", "row_reward", "row_parent", "env_state",
+                    "grass_xy", "grass_energy")
+
     def host_tables(self, b=None):
         """Small per-env tables copied to the host as numpy arrays."""
         sl = slice(None) if b is None else slice(b, b + 1)
-        names = ["row_xy", "row_energy", "row_id", "row_cumrew", "row_flags", "row_reward", "row_parent", "env_state",
-                 "grass_xy", "grass_energy"]
-        return {n: getattr(self, n)[sl].cpu().numpy() for n in names}
+        return {n: getattr(self, n)[sl].cpu().numpy() for n in self._HOST_TABLES}
 
     def records(self, b, tables=None):
         """The returned dicts of env b's last call as an ordered list of

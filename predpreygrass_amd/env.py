@@ -36,12 +36,7 @@ except Exception:  # ray is an optional dependency; same fallback idea as the re
 
 try:
     import gymnasium as _gym  # type: ignore
-
-    def _box(shape):
-        return _gym.spaces.Box(low=0.0, high=100.0, shape=shape, dtype=np.float64)
-
-    def _discrete(n):
-        return _gym.spaces.Discrete(n)
+    _Box, _Discrete = _gym.spaces.Box, _gym.spaces.Discrete
 except Exception:
     class _Box:  # predpreygrass_rllib_env.py:88-89
         def __init__(self, low, high, shape, dtype):
@@ -64,11 +59,13 @@ except Exception:
         def sample(self):
             return int(np.random.randint(self.n))
 
-    def _box(shape):
-        return _Box(0.0, 100.0, shape, np.float64)
 
-    def _discrete(n):
-        return _Discrete(n)
+def _box(shape, high=100.0, dtype=np.float64):
+    return _Box(low=0.0, high=high, shape=shape, dtype=dtype)
+
+
+def _discrete(n):
+    return _Discrete(n)
 
 
 def _parse(name: str):
@@ -89,7 +86,56 @@ def _pred_capacity_for(cfg, pred_capacity) -> int:
     return 64
 
 
-class PredPreyGrass(_MultiAgentEnvBase):
+class _TableViews:
+    """What the dict classes of both generations read from the tables of the last fetch (`self._tables`, batch index 0), the records
+    of the last call (`self._records`: name, species, row, reward, terminated, truncated) and `self._insertion_order` (the agent ids in
+    the order the reference's dicts first saw them); `self._b` is the batch."""
+
+    _spawn_ref = "predpreygrass_rllib_env.py:401-405"   # where the reference fails when a newborn finds no free cell
+
+    def _check_status(self, es):
+        status = int(es[_abi.ENV_STATUS])
+        if status & (_abi.STATUS_PRED_OVERFLOW | _abi.STATUS_PREY_OVERFLOW):
+            raise RuntimeError("agent row capacity exceeded: construct the env with a larger prey_capacity")
+        if status & _abi.STATUS_FAILED_SPAWN:
+            raise TypeError(f"no free cell for a newborn (the reference fails at {self._spawn_ref})")
+
+    def _live(self):
+        """name -> row of the [B,S] tables, of the agents alive after the last call."""
+        cp = self._b.pred_capacity
+        return {name: cp * sp + row for name, sp, row, _, te, _ in self._records if not te}
+
+    # viewer-facing attributes (random_policy.py:32-39, evaluate_ppo_from_checkpoint_debug.py:190-197; RQ:93-98,108-109)
+    @property
+    def agent_positions(self):
+        live, xy = self._live(), self._tables["row_xy"][0]
+        return {n: (int(xy[live[n]]) >> 8, int(xy[live[n]]) & 255) for n in self._insertion_order if n in live}
+
+    @property
+    def predator_positions(self):
+        return {k: v for k, v in self.agent_positions.items() if "predator" in k}
+
+    @property
+    def prey_positions(self):
+        return {k: v for k, v in self.agent_positions.items() if "prey" in k}
+
+    @property
+    def agent_energies(self):
+        live, t = self._live(), self._tables
+        return {n: float(t["row_energy"][0][live[n]]) for n in self._insertion_order if n in live}
+
+    @property
+    def grass_positions(self):
+        t = self._tables
+        return {f"grass_{k}": (int(t["grass_xy"][0][k]) >> 8, int(t["grass_xy"][0][k]) & 255) for k in range(self._b.n_grass)}
+
+    @property
+    def grass_energies(self):
+        t = self._tables
+        return {f"grass_{k}": float(t["grass_energy"][0][k]) for k in range(self._b.n_grass)}
+
+
+class PredPreyGrass(_TableViews, _MultiAgentEnvBase):
     def __init__(self, config=None, *, device=None, batched: BatchedPredPreyGrass | None = None, index: int = 0,
                  prey_capacity: int | None = None, _library=None, pred_capacity: int | None = None):
         super().__init__()
@@ -221,11 +267,7 @@ class PredPreyGrass(_MultiAgentEnvBase):
             op, oq = obs[0][i], obs[1][i]
         self._tables = t
         es = t["env_state"][0]
-        status = int(es[_abi.ENV_STATUS])
-        if status & (_abi.STATUS_PRED_OVERFLOW | _abi.STATUS_PREY_OVERFLOW):
-            raise RuntimeError("agent row capacity exceeded: construct the env with a larger prey_capacity")
-        if status & _abi.STATUS_FAILED_SPAWN:
-            raise TypeError("no free cell for a newborn (the reference fails at predpreygrass_rllib_env.py:401-405)")
+        self._check_status(es)
         obs, rew, term, trunc = {}, {}, {}, {}
         # one float64 copy of each species' blocks in use (the fetch buffer is reused by the next call); the dict entries are its rows
         ops = (np.array(op, dtype=np.float64), np.array(oq, dtype=np.float64))
@@ -272,27 +314,6 @@ class PredPreyGrass(_MultiAgentEnvBase):
         trunc["__all__"] = was_trunc_call
         return obs, rew, term, trunc, {}
 
-    def _live(self):
-        b, t = self._b, self._tables
-        cp = b.pred_capacity
-        out = {}
-        for name, ty, row, _, te, _ in self._records:
-            if not te:
-                out[name] = row if ty == PREDATOR else cp + row
-        return out
-
-    # viewer-facing attributes (random_policy.py:32-39, evaluate_ppo_from_checkpoint_debug.py:190-197)
-    @property
-    def agent_positions(self):
-        live, t = self._live(), self._tables
-        order = [n for n in self._insertion_order if n in live]  # dict insertion order of the reference
-        return {n: (int(t["row_xy"][0][live[n]]) >> 8, int(t["row_xy"][0][live[n]]) & 255) for n in order}
-
-    @property
-    def agent_energies(self):
-        live, t = self._live(), self._tables
-        return {n: float(t["row_energy"][0][live[n]]) for n in self._insertion_order if n in live}
-
     @property
     def agent_parent(self):
         """child id -> parent id of the kickback variant (…plus_kickback/predpreygrass_rllib_env.py:86-91)."""
@@ -302,25 +323,6 @@ class PredPreyGrass(_MultiAgentEnvBase):
             if n in live and int(t["row_parent"][0][live[n]]) >= 0:
                 out[n] = n.rsplit("_", 1)[0] + "_%d" % int(t["row_parent"][0][live[n]])
         return out
-
-    @property
-    def predator_positions(self):
-        return {k: v for k, v in self.agent_positions.items() if k.startswith("predator")}
-
-    @property
-    def prey_positions(self):
-        return {k: v for k, v in self.agent_positions.items() if k.startswith("prey")}
-
-    @property
-    def grass_positions(self):
-        t = self._tables
-        return {f"grass_{k}": (int(t["grass_xy"][0][k]) >> 8, int(t["grass_xy"][0][k]) & 255)
-                for k in range(self.initial_num_grass)}
-
-    @property
-    def grass_energies(self):
-        t = self._tables
-        return {f"grass_{k}": float(t["grass_energy"][0][k]) for k in range(self.initial_num_grass)}
 
     @property
     def grid_world_state(self):

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from .batched import _alloc_on
 
 
 class _Named(torch.nn.Module):
@@ -256,25 +257,16 @@ class FusedPolicy:
         (`PPG_POLICY_SEED_ON_DEVICE`): what a step captured into a HIP graph needs (`GraphedPolicyStep`)."""
         envs = list(envs) if isinstance(envs, (list, tuple)) else [envs]
         acts = [e.actions for e in envs] if actions is None else list(actions)
-        for e, a in zip(envs, acts):
-            if a.dtype != torch.int8 or tuple(a.shape) != (e.batch_size, e.S) or not a.is_contiguous() or a.device != e.device:
-                raise ValueError("actions must be contiguous int8 tensors [B_k, S] on the envs' device")
         n = len(envs)
+        aptr = (C.c_void_p * n)(*[e._tensor_arg("actions", a, (torch.int8,), (e.batch_size, e.S)) for e, a in zip(envs, acts)])
         handles = (C.c_void_p * n)(*[e._handle for e in envs])
-        aptr = (C.c_void_p * n)(*[a.data_ptr() for a in acts])
         lg = [None, None]
         if want_logits:
-            # the buffers are zero-filled on the stream the kernels run on (so the fill cannot race with their writes and the
-            # caching allocator knows which stream uses the blocks); a raw hipStream_t handle: fill on the current stream and
-            # let the host wait for it
-            on = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.current_stream(self.device)
-            with torch.cuda.stream(on):
-                for t, net in enumerate(self.nets):
-                    if net is not None:
-                        cap = sum(e.batch_size * (e.prey_capacity if t else e.pred_capacity) for e in envs)
-                        lg[t] = torch.zeros((cap, net.n_actions), dtype=torch.float32, device=self.device)
-            if stream is not None and not isinstance(stream, torch.cuda.Stream):
-                on.synchronize()
+            def cap(t):
+                return sum(e.batch_size * (e.prey_capacity if t else e.pred_capacity) for e in envs)
+            # zero-filled on the stream the kernels run on, so that the fill cannot race with their writes
+            lg = _alloc_on(self.device, stream, lambda: [None if net is None else torch.zeros(
+                (cap(t), net.n_actions), dtype=torch.float32, device=self.device) for t, net in enumerate(self.nets)])
         flags = _abi.POLICY_SAMPLE if sample else _abi.POLICY_ARGMAX
         if isinstance(seed, torch.Tensor):
             if seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != self.device:

@@ -7,7 +7,6 @@ ppg_step_uniforms); all environment logic runs in predpreygrass_amd/csrc/ppg_ker
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import numpy as np
@@ -127,19 +126,13 @@ class BatchedRedQueen(BatchedPredPreyGrass):
         mask_observation_with_visibility), per-agent move infos in `row_info`.  Walls are given with `set_walls`.
         pred_capacity: 64 or 128 predator rows per env (128: no walls, prey_capacity 128 or 256, one wave per env)."""
         cfg = resolve_config(config)
-        self.config = cfg
-        self._obs_spread = int(obs_spread)   # (BatchedPredPreyGrass: observation tensors on spread physical pages)
+        self._init_common(cfg, batch_size, device, obs_dtype, _library, obs_spread)
         self.walls = bool(walls)
         self.vis_channel = self.walls and bool(cfg.get("include_visibility_channel", False))   # WO:104
-        self.obs_channels = 5 if self.vis_channel else 4
-        self.batch_size = int(batch_size)
-        self._init_device(device, obs_dtype, _library)
-        self.grid_size = int(cfg["grid_size"])
-        self.Rp, self.Rq = int(cfg["predator_obs_range"]), int(cfg["prey_obs_range"])
+        self.obs_channels = self.obs_channels_pred = self.obs_channels_prey = 5 if self.vis_channel else 4
         self.n_initial = [int(cfg[k]) for k in _INITIAL_KEYS]
         self.n_possible = [int(cfg[k]) for k in _POSSIBLE_KEYS]
         self.P0, self.Q0 = self.n_initial[0] + self.n_initial[1], self.n_initial[2] + self.n_initial[3]
-        self.n_grass = int(cfg["initial_num_grass"])
         self.cooldown = int(cfg["reproduction_cooldown_steps"])
         self.action_ranges = (int(cfg["type_1_action_range"]), int(cfg["type_2_action_range"]))
         self._alloc_buffers(prey_capacity, pred_capacity)
@@ -173,18 +166,8 @@ class BatchedRedQueen(BatchedPredPreyGrass):
     def set_placement(self, pred_xy, prey_xy, grass_xy, episode=0):
         """reset() with a given placement (RQ:151-195): predators / prey in creation order (type 1 then type 2),
         grass in id order; arrays [B,P0,2], [B,Q0,2], [B,n_grass,2] of (x, y)."""
-        B, G = self.batch_size, self.grid_size
-        pred = np.asarray(pred_xy, dtype=np.int64).reshape(B, self.P0, 2)
-        prey = np.asarray(prey_xy, dtype=np.int64).reshape(B, self.Q0, 2)
-        grass = np.asarray(grass_xy, dtype=np.int64).reshape(B, self.n_grass, 2)
-        for a in (pred, prey, grass):
-            if a.size and (a.min() < 0 or a.max() >= G):
-                raise ValueError("position outside the grid")
-        gcell = grass[..., 0] * G + grass[..., 1]
-        for b in range(B):
-            if len(np.unique(gcell[b])) != self.n_grass:
-                raise ValueError("grass positions must be unique")
-        S, cp = self.S, self.pred_capacity
+        pred, prey, grass = self._placement_arrays(pred_xy, prey_xy, grass_xy)
+        B, S, cp = self.batch_size, self.S, self.pred_capacity
         xy = np.zeros((B, S), dtype=np.int16)
         en = np.zeros((B, S), dtype=np.float64)
         ids = np.zeros((B, S), dtype=np.int32)
@@ -266,41 +249,21 @@ class BatchedRedQueen(BatchedPredPreyGrass):
         if uniforms is None:
             return super().step(actions, random_actions=random_actions, auto_reset=auto_reset, act_rank=act_rank,
                                 stream=stream)
-        if uniforms.dtype != torch.float64 or uniforms.dim() != 2 or uniforms.shape[0] != self.batch_size or \
-                uniforms.device != self.device or not uniforms.is_contiguous():
-            raise ValueError("uniforms must be a contiguous float64 tensor [B,U] on the env's device")
-        flags = (_abi.STEP_RANDOM_ACTIONS if random_actions else 0) | (_abi.STEP_AUTO_RESET if auto_reset else 0)
-        ptr = None
-        if not random_actions:
-            if actions is None:
-                actions = self.actions
-            if actions.dtype != torch.int8 or tuple(actions.shape) != (self.batch_size, self.S) or \
-                    actions.device != self.device or not actions.is_contiguous():
-                raise ValueError(f"actions must be a contiguous int8 tensor [{self.batch_size},{self.S}] on {self.device}")
-            ptr = C.c_void_p(actions.data_ptr())
-        rank_ptr = None
-        if act_rank is not None:
-            if act_rank.dtype != torch.uint8 or tuple(act_rank.shape) != (self.batch_size, self.S) or \
-                    act_rank.device != self.device or not act_rank.is_contiguous():
-                raise ValueError("act_rank must be a contiguous uint8 tensor [B,S] on the env's device")
-            rank_ptr = C.c_void_p(act_rank.data_ptr())
-        self._check(self._lib.ppg_step_uniforms(self._handle, ptr, rank_ptr, C.c_void_p(uniforms.data_ptr()),
-                                                int(uniforms.shape[1]), flags, self._stream(stream)), "ppg_step_uniforms")
+        u = self._tensor_arg("uniforms", uniforms, (torch.float64,), (self.batch_size, None))
+        flags, ptr, rank = self._step_args(actions, random_actions, auto_reset, act_rank)
+        self._check(self._lib.ppg_step_uniforms(self._handle, ptr, rank, u, int(uniforms.shape[1]), flags, self._stream(stream)),
+                    "ppg_step_uniforms")
         return self
 
-    def rollout(self, n_steps, actions=None, random_actions=False, auto_reset=False, stream=None):
-        """`n_steps` transitions in ONE launch: the fused form of the cooperative step kernel (the handle's wave plan must be
-        cooperative with four waves -- the default on a full GPU, else `set_wave_plan(4, 0, 2)`; not for the walls variant).  Same
-        result as `n_steps` calls of step(): actions from the device-side uniform random policy or an int8 tape [n_steps, B, S],
-        reproduction uniforms from the device's Philox streams."""
-        return super().rollout(n_steps, actions=actions, random_actions=random_actions, auto_reset=auto_reset, stream=stream)
-
     # ------------------------------------------------------------------
-    def host_tables(self, b=None):
-        sl = slice(None) if b is None else slice(b, b + 1)
-        names = ["row_xy", "row_energy", "row_id", "row_key", "row_cumrew", "row_flags", "row_reward", "row_lastrep",
-                 "row_info", "env_state", "grass_xy", "grass_energy"]
-        return {n: getattr(self, n)[sl].cpu().numpy() for n in names}
+    _HOST_TABLES = ("row_xy", "row_energy", "row_id", "row_key", "row_cumrew", "row_flags", "row_reward", "row_lastrep",
+                    "row_info", "env_state", "grass_xy", "grass_energy")
+
+    def _fetch_fields(self):
+        f = super()._fetch_fields() + [("row_lastrep", "<i4", self.S)]   # (ppg_create_gen2's records)
+        if self.walls:
+            f += [("row_info", "u1", self.S), ("wall_bits", "<i4", int(self.wall_bits.shape[1]))]
+        return f
 
     def records(self, b, tables=None):
         """The returned dicts of env b's last call as an ordered list of (name, species, row, reward, terminated,
@@ -337,28 +300,11 @@ class BatchedRedQueen(BatchedPredPreyGrass):
 # the reference's class on top of the kernels
 # ---------------------------------------------------------------------------------------------------------
 
-from .env import _MultiAgentEnvBase  # noqa: E402  (RLlib's MultiAgentEnv when ray is installed)
+from .env import _MultiAgentEnvBase, _TableViews, _box, _discrete  # noqa: E402  (RLlib's MultiAgentEnv when ray is installed)
 from .placement import reference_placement  # noqa: E402
 
-try:
-    import gymnasium as _gym  # type: ignore
 
-    def _box(shape):
-        return _gym.spaces.Box(low=0, high=100.0, shape=shape, dtype=np.float32)  # RQ:963,967
-
-    def _discrete(n):
-        return _gym.spaces.Discrete(n)
-except Exception:
-    from .env import _Box, _Discrete  # noqa: E402
-
-    def _box(shape):
-        return _Box(0, 100.0, shape, np.float32)
-
-    def _discrete(n):
-        return _Discrete(n)
-
-
-class PredPreyGrass(_MultiAgentEnvBase):
+class PredPreyGrass(_TableViews, _MultiAgentEnvBase):
     """`PredPreyGrass(config)` of red_queen/predpreygrass_rllib_env.py (class :14, reset :151, step :197): same
     constructor, dict layouts, id strings, dict ordering, float32 observations and viewer-facing attributes, with the
     transition running on the GPU.  `reset(seed=s)` places the agents where the reference does and seeds the same
@@ -368,6 +314,7 @@ class PredPreyGrass(_MultiAgentEnvBase):
     ``per_step_agent_data``, ``agent_ages``, offspring lists ... RQ:99-116) are kept by a host-side mirror
     (rq_analytics.AgentAnalytics) from the tables every call fetches anyway; ``analytics=False`` switches them off."""
 
+    _spawn_ref = "RQ:751-760"
     _walls = False                 # walls_occlusion.PredPreyGrass sets this
     _require_all_actions = True    # RQ:279 fails for a live agent without an action
 
@@ -390,8 +337,8 @@ class PredPreyGrass(_MultiAgentEnvBase):
             setattr(self, k, cfg[k])                                               # RQ:36-78
         self.type_1_act_range, self.type_2_act_range = b.action_ranges               # RQ:85-86
         self.possible_agents = [f"{POOLS[p]}_{i}" for p in (0, 1, 2, 3) for i in range(b.n_possible[p])]  # RQ:941-955
-        self._pspace = _box((b.obs_channels, b.Rp, b.Rp))
-        self._qspace = _box((b.obs_channels, b.Rq, b.Rq))
+        self._pspace = _box((b.obs_channels, b.Rp, b.Rp), 100.0, np.float32)   # RQ:963,967
+        self._qspace = _box((b.obs_channels, b.Rq, b.Rq), 100.0, np.float32)
         self._aspace = {1: _discrete(self.type_1_act_range ** 2), 2: _discrete(self.type_2_act_range ** 2)}  # RQ:974-985
         self.observation_spaces = {a: (self._pspace if "predator" in a else self._qspace) for a in self.possible_agents}
         self.action_spaces = {a: self._aspace[int(a[5])] for a in self.possible_agents}
@@ -522,11 +469,7 @@ class PredPreyGrass(_MultiAgentEnvBase):
         t, fp, fq = b.fetch(0, 1)   # ONE device->host copy: the tables and the observation rows in use (ppg_fetch)
         self._tables = t
         es = t["env_state"][0]
-        status = int(es[_abi.ENV_STATUS])
-        if status & (_abi.STATUS_PRED_OVERFLOW | _abi.STATUS_PREY_OVERFLOW):
-            raise RuntimeError("agent row capacity exceeded: construct the env with a larger prey_capacity")
-        if status & _abi.STATUS_FAILED_SPAWN:
-            raise TypeError("no free cell for a newborn (the reference fails at RQ:751-760)")
+        self._check_status(es)
         recs = b.records(0, t)
         op, oq = fp[0], fq[0]
         obs, rew, term, trunc = {}, {}, {}, {}
@@ -559,44 +502,10 @@ class PredPreyGrass(_MultiAgentEnvBase):
     def _finish_outputs(self, recs, tables, rew, term, trunc, truncated_call):
         return {}   # RQ:198,299: infos stays empty
 
-    def _live(self):
-        cp = self._b.pred_capacity
-        return {name: cp * sp + row for name, sp, row, _, te, _ in self._records if not te}
-
-    # viewer-facing attributes (RQ:93-98,108-109)
-    @property
-    def agent_positions(self):
-        live, t = self._live(), self._tables
-        return {n: (int(t["row_xy"][0][live[n]]) >> 8, int(t["row_xy"][0][live[n]]) & 255)
-                for n in self._insertion_order if n in live}
-
-    @property
-    def predator_positions(self):
-        return {k: v for k, v in self.agent_positions.items() if "predator" in k}
-
-    @property
-    def prey_positions(self):
-        return {k: v for k, v in self.agent_positions.items() if "prey" in k}
-
-    @property
-    def agent_energies(self):
-        live, t = self._live(), self._tables
-        return {n: float(t["row_energy"][0][live[n]]) for n in self._insertion_order if n in live}
-
     @property
     def agent_last_reproduction(self):
         live, t = self._live(), self._tables
         return {n: int(t["row_lastrep"][0][live[n]]) for n in self._insertion_order if n in live}
-
-    @property
-    def grass_positions(self):
-        t = self._tables
-        return {f"grass_{k}": (int(t["grass_xy"][0][k]) >> 8, int(t["grass_xy"][0][k]) & 255) for k in range(self._b.n_grass)}
-
-    @property
-    def grass_energies(self):
-        t = self._tables
-        return {f"grass_{k}": float(t["grass_energy"][0][k]) for k in range(self._b.n_grass)}
 
     @property
     def grid_world_state(self):

@@ -26,7 +26,6 @@ import ctypes as C
 
 import torch
 
-from . import _abi
 from .batched import BatchedPredPreyGrass
 from .distributed import shard_range
 
@@ -114,6 +113,11 @@ class SubBatchedPredPreyGrass:
         each sub-batch's own `.actions` tensor).  All sub-batches are launched by ONE C call
         (ppg_step_many), sub-batch k on stream k."""
         n = len(self.subs)
+        flags = self.subs[0]._step_args(None, random_actions, auto_reset)[0]
+        acts = None
+        if actions is not None and not random_actions:   # (checked here: the CPU and the GPU path both see it)
+            acts = (C.c_void_p * n)(*[self.subs[k]._tensor_arg(f"actions[{k}]", a, (torch.int8,), (self.subs[k].batch_size, self.subs[k].S))
+                                      for k, a in enumerate(actions)])
         if self.streams[0] is None:   # CPU (emulated kernel, tests)
             for k, e in enumerate(self.subs):
                 e.step(None if actions is None else actions[k], random_actions=random_actions, auto_reset=auto_reset)
@@ -122,17 +126,8 @@ class SubBatchedPredPreyGrass:
             self._c_handles = (C.c_void_p * n)(*[e._handle for e in self.subs])
             self._c_streams = (C.c_void_p * n)(*[s.cuda_stream for s in self.streams])
             self._c_own_actions = (C.c_void_p * n)(*[e.actions.data_ptr() for e in self.subs])
-        flags = (_abi.STEP_RANDOM_ACTIONS if random_actions else 0) | (_abi.STEP_AUTO_RESET if auto_reset else 0)
-        if random_actions:
-            acts = None
-        elif actions is None:
+        if acts is None and not random_actions:
             acts = self._c_own_actions
-        else:
-            for k, a in enumerate(actions):
-                if a.dtype != torch.int8 or tuple(a.shape) != (self.subs[k].batch_size, self.subs[k].S) or \
-                        not a.is_contiguous() or a.device != self.subs[k].device:
-                    raise ValueError("actions[k] must be a contiguous int8 tensor [B_k, S] on the env's device")
-            acts = (C.c_void_p * n)(*[a.data_ptr() for a in actions])
         # whatever the caller enqueued on the current stream (a policy writing the action tensors, edits of env_state)
         # happens before the step kernels of the sub-batch streams
         self._order_behind_current()
