@@ -1046,6 +1046,12 @@ static int ppg_policy_fail(ppg_policy *p, int code, const char *fmt, ...) {
     return code;
 }
 
+// ppg_policy_act with two policies: a failure is also reported through ppg_policy_last_error(NULL), whichever of them it came from
+static int ppg_policy_mirror(const ppg_policy *p, int rc) {
+    if (rc != PPG_OK) memcpy(g_ppg_policy_error, p->err, sizeof g_ppg_policy_error);
+    return rc;
+}
+
 #define PPG_POL_TRY(p, call)                                                                              \
     do {                                                                                                  \
         hipError_t e_ = (call);                                                                           \
@@ -1161,17 +1167,7 @@ int ppg_policy_create(int32_t device, int32_t obs_range, int32_t n_actions, cons
     return ppg_policy_create_layout(device, obs_range, n_actions, PPG_POLICY_LAYOUT_CHW, w, out);
 }
 
-int ppg_policy_describe(const ppg_policy_spec *spec, int32_t *out, int32_t n);
 int ppg_policy_destroy(ppg_policy *p);
-// ppg_policy_describe restates the kernel choice and the layout without a device: a policy is only handed out if the two agree
-static int ppg_policy_matches_description(ppg_policy *p, const ppg_policy_spec *spec) {
-    int32_t d[4] = {-1, -1, -1, -1};
-    const int family = p->pipe ? 3 : p->direct;
-    if (ppg_policy_describe(spec, d, 4) != PPG_OK || d[0] != family || d[1] != p->base.ST || d[2] != p->lds_bytes || d[3] != (p->pipe ? 512 : 256))
-        return ppg_policy_fail(nullptr, PPG_EHIP, "internal: ppg_policy_describe says family %d, %d samples per sub-group, %d bytes of LDS; built %d, %d, %d",
-                               d[0], d[1], d[2], family, p->base.ST, p->lds_bytes);
-    return PPG_OK;
-}
 
 #ifndef PPG_POLICY_PIPE
 #define PPG_POLICY_PIPE 1   // (0: A/B builds without the two-role pipeline)
@@ -1208,6 +1204,19 @@ static bool ppg_slot_table(int ST, int IH, int IW, int stride_elems, std::vector
     for (int r = 0; r < 16; ++r)
         for (size_t k = 0; k < cls[r].size(); ++k) tab[16 * k + r] = cls[r][k];
     return true;
+}
+
+// samples per sub-group of the direct-head kernels, at most st_max: the most samples per round of position tiles (four wavefronts take a
+// tile of 32 positions each); of equal scores the largest
+static int ppg_subgroup_samples(int st_max, int P) {
+    int st = st_max;
+    double best = 0.0;
+    for (int c = st_max; c >= 1; --c) {
+        const int tiles = (c * P + 31) / 32, rounds = (tiles + 3) / 4;
+        const double score = (double)c / rounds;
+        if (score > best * 1.0001) { best = score; st = c; }
+    }
+    return st;
 }
 
 // LDS layout of the two-role pipeline kernels (ppg_policy_pipe.h) for rows of C x R x R elements read as P positions; blk = elements of
@@ -1248,13 +1257,7 @@ static bool ppg_pipe_layout_at(int C, int R, int P, int blk, int f_elems, int ta
     while (st_cap > 1 && st_cap * P > 256) --st_cap;   // a role-B thread stages one position
     if (st_cap < 1 || P > 256) return false;
     {
-        int st = st_cap;
-        double best = 0.0;
-        for (int c = st_cap; c >= 1; --c) {   // the most samples per round of position tiles (four wavefronts a tile each)
-            const int tiles = (c * P + 31) / 32, rounds = (tiles + 3) / 4;
-            const double score = (double)c / rounds;
-            if (score > best * 1.0001) { best = score; st = c; }
-        }
+        const int st = ppg_subgroup_samples(st_cap, P);
         int raw_bytes = chunks ? (st * row_bf16 + 15) / 16 * 16 : 0;
         const int cpr = row_bf16 / 8;   // 8-byte chunks per row; the role-B threads cover floor(256 / cpr) samples per load
         K.pipe_slots = chunks && cpr <= 256 ? 256 / cpr : 0;
@@ -1305,6 +1308,133 @@ static int ppg_policy_check_spec(const ppg_policy_spec &sp, bool need_weights) {
     return PPG_OK;
 }
 
+// Everything the SHAPE of a network decides, device-free: ppg_policy_create_spec builds what this says, ppg_policy_describe prints it and
+// ppg_policy_pack(PPG_POLICY_PACK_SLOTS) returns its slot table.
+struct ppg_policy_layout {
+    int family;                       // 0: the FC chain; 1: direct head; 2: direct head behind more than three convolutions; 3: the two-role pipeline
+    int threads;                      // per workgroup
+    int lds_bytes;                    // dynamic LDS of a workgroup
+    int wgs_per_cu;                   // 1: a workgroup takes a whole CU's LDS (grid = CUs); 2: half of it (grid = 2 x CUs)
+    ppgpol::PolParams K;              // the geometry only, the rest zero: Wp, Wp2, flat_c, kflat_steps, head_mt, ST, range_tile, off_*, sample_stride, pipe_*, slot_tiles
+    std::vector<uint16_t> slot_tab;   // family 3: ppg_slot_table
+};
+
+// sp: a spec ppg_policy_check_spec accepts.  allow_pipe = false sends a network of the two-role pipeline to the one-role direct-head
+// kernels instead.  PPG_EINVAL: the image is too large for one sample in LDS.
+static int ppg_policy_layout_of(const ppg_policy_spec &sp, bool allow_pipe, ppg_policy_layout &L) {
+    const int R = sp.obs_range, C = sp.obs_channels, hwc = sp.layout == PPG_POLICY_LAYOUT_HWC;
+    // the image the convolutions run on: R x R with C channels, or (channels-last) C x R with R channels
+    const int IH = hwc ? C : R, IW = R, CIN = hwc ? R : C, P = IH * IW;
+    ppgpol::PolParams &K = L.K;
+    memset(&K, 0, sizeof K);
+    L.slot_tab.clear();
+    L.threads = 256;
+    if (sp.n_fc > 1) {
+        // FC chain.  LDS: tile table + max(activation images of ST samples, H, FC1 staging); ST as large as 2 workgroups per CU (80 KB each) allow
+        K.Wp = IW + 2; K.Wp2 = (IH + 2) * (IW + 2);
+        const int per_sample = 6 * K.Wp2 * 8 * 2;                       // X (4 blocks) + Y (2 blocks), bytes
+        const int h_bytes = ppgpol::TILE * ppgpol::HSTRIDE * 2;
+        int st = (78 * 1024 - ppgpol::TILE * 16) / per_sample;
+        if (st < 1) st = 1;
+        if (st > 16) st = 16;
+        while (st > 1 && st * P > 512) --st;   // the staging of a sub-group gives every thread at most two positions
+        K.ST = st;
+        const int img = st * per_sample, fc1_stage = 3 * ppgpol::FC1_BUF;
+        int overlay = img > h_bytes ? img : h_bytes;
+        if (fc1_stage > overlay) overlay = fc1_stage;
+        L.family = 0; L.wgs_per_cu = 2; L.lds_bytes = ppgpol::TILE * 16 + overlay;
+        return PPG_OK;
+    }
+    // direct head: area F is [position][flat_c channels], read by the head in k-steps of 32 features, 16 actions per tile
+    K.flat_c = (sp.conv_out[sp.n_conv - 1] + 7) / 8 * 8; K.kflat_steps = (P * K.flat_c + 31) / 32; K.head_mt = (sp.n_actions + 15) / 16;
+    // LDS region of a sample: X (4 blocks) | Y (2 blocks) | F | [D0 | D1] -- padded pitch W + 1 (ppg_policy_direct.h)
+    K.Wp = IW + 1; K.Wp2 = (IH + 2) * (IW + 1) + 1;
+    const int blk = K.Wp2 * 8, f_elems = K.kflat_steps * 32 + 8;   // (+ 8: consecutive samples' fragments fall into different banks)
+    K.off_x = 0; K.off_y = 4 * blk; K.off_f = 6 * blk; K.off_d0 = K.off_f + f_elems; K.off_d1 = K.off_d0 + 8 * blk;
+    K.sample_stride = K.off_f + f_elems + (sp.n_conv > 3 ? 8 * blk : 0) + (sp.n_conv > 4 ? 8 * blk : 0);
+    const int tail_slack = 18 * 32 * 2;   // bytes behind the last sample's region: the head's unconditional fragment reads end there
+    // the two-role pipeline (ppg_policy_pipe.h): three convolutions, up to 16 actions, a wavefront's quarter of the head's k-steps in 18
+    // fragments, up to nine input channels (Conv1X); region of a sample: X0 | X1 (4 blocks each) | Y (2 blocks) | F0 | F1
+    if (allow_pipe && sp.n_conv == 3 && K.head_mt == 1 && (K.kflat_steps + 3) / 4 <= 18 && CIN <= 9 &&
+        ppg_pipe_layout(C, R, P, blk, f_elems, tail_slack, K, &L.lds_bytes, &L.slot_tab)) {
+        L.family = 3; L.threads = 512; L.wgs_per_cu = 1;
+        return PPG_OK;
+    }
+    const int fixed = ppgpol::TILE * 16 + K.head_mt * 4096 + 4096 + tail_slack;   // table, partial logits, dconv's dummy slots
+    const bool w1 = PPG_DIRECT_W1;   // one workgroup per CU with all of its LDS (ppg_policy_direct.h)
+    int st_max = ((w1 ? 160 : 80) * 1024 - fixed) / (K.sample_stride * 2);
+    if (st_max > 16) st_max = 16;                // (the head's 16 sample columns)
+    while (st_max > 1 && st_max * P > (w1 ? 512 : 256)) --st_max;   // a thread stages at most two / one positions
+    if (st_max < 1)
+        return ppg_policy_fail(nullptr, PPG_EINVAL, "a %d x %d image with %d convolutions needs %d bytes of LDS per sample: too large", IH, IW, sp.n_conv, K.sample_stride * 2);
+    const int st = ppg_subgroup_samples(st_max, P);
+    K.ST = st;
+    K.range_tile = st * (ppgpol::TILE / st);   // whole sub-groups per tile
+    L.family = sp.n_conv > 3 ? 2 : 1; L.wgs_per_cu = w1 ? 1 : 2; L.lds_bytes = fixed + st * K.sample_stride * 2;
+    return PPG_OK;
+}
+
+// The weights of a spec in the kernels' operand order, one vector per device array: the convolutions, then up to three linear layers (a
+// direct head: wh, whw), conv1 in the pipeline's form, the pipeline's slot table (ppg_policy_layout::slot_tab: not a weight, uploaded with them)
+enum { PPG_FRAG_FC = PPG_POLICY_MAX_CONV, PPG_FRAG_CONV1X = PPG_POLICY_MAX_CONV + 3, PPG_FRAG_SLOTS, PPG_FRAG_N };
+struct ppg_policy_fragments {
+    std::vector<uint16_t> f[PPG_FRAG_N];
+    std::vector<float> bias;   // FC chain: b1, b2, b3 at [0], [256], [512]; direct: head bias at [512]; the pipeline's conv1 bias at [544]
+};
+
+// sp: a spec ppg_policy_check_spec accepts, weight pointers included
+static void ppg_policy_fragments_of(const ppg_policy_spec &sp, ppg_policy_fragments &F) {
+    const int hwc = sp.layout == PPG_POLICY_LAYOUT_HWC, n_actions = sp.n_actions;
+    const int CIN = hwc ? sp.obs_range : sp.obs_channels, P = (hwc ? sp.obs_channels : sp.obs_range) * sp.obs_range;
+    const int cout_last = sp.conv_out[sp.n_conv - 1];
+    const int flat = P * cout_last;   // features behind the flatten
+    const bool nhwc = sp.flatten == PPG_POLICY_FLATTEN_NHWC;
+    std::vector<float> &bias = F.bias;
+    bias.assign(256 + 256 + 32 + 16, 0.0f);
+    int ci = CIN;
+    for (int l = 0; l < sp.n_conv; ++l) {   // input channel blocks: conv1 one or two, then 2, 4, 8; output row tiles: 1, 1, then 2
+        ppg_pack_conv(sp.conv_w[l], sp.conv_b[l], sp.conv_out[l], ci, l == 0 ? (CIN > 8 ? 2 : 1) : l == 1 ? 2 : l == 2 ? 4 : 8, l < 2 ? 1 : 2, F.f[l]);
+        ci = sp.conv_out[l];
+    }
+    if (CIN <= 9) {
+        ppg_pack_conv1x(sp.conv_w[0], sp.conv_out[0], CIN, F.f[PPG_FRAG_CONV1X]);
+        for (int c = 0; c < sp.conv_out[0] && c < 16; ++c) bias[544 + c] = sp.conv_b[0][c];
+    }
+    if (sp.n_fc == 1) {
+        std::vector<uint16_t> &wh = F.f[PPG_FRAG_FC], &whw = F.f[PPG_FRAG_FC + 1];
+        ppg_pack_head(sp.fc_w[0], n_actions, P, cout_last, nhwc, wh);
+        for (int a = 0; a < n_actions; ++a) bias[512 + a] = sp.fc_b[0][a];
+        // whw: wavefront w owns k-steps [w per, (w + 1) per) of action tile 0, its first 18 ride in registers (ppg_policy_direct.h)
+        const int ksteps = (P * ((cout_last + 7) / 8 * 8) + 31) / 32, HFR = 18, per = (ksteps + 3) / 4;
+        whw.assign((size_t)4 * HFR * 64 * 8, 0);
+        for (int w = 0; w < 4; ++w)
+            for (int i = 0; i < HFR && i < per; ++i) {
+                const int ks = w * per + i;
+                if (ks >= ksteps) break;
+                memcpy(&whw[((size_t)w * HFR + i) * 64 * 8], &wh[(size_t)ks * 64 * 8], 64 * 8 * 2);
+            }
+        return;
+    }
+    // FC1: the K order is the scratch slot's [row tile of conv3][position][32 channels]; hidden widths are zero-padded to 256
+    const int h1 = sp.fc_out[0], h2 = sp.n_fc == 3 ? sp.fc_out[1] : 0;
+    const float *w1 = sp.fc_w[0];
+    // feature index of (channel c, position q) behind the flatten, or -1 for a padding channel
+    auto feature = [=](int c, int q) { return c >= cout_last ? -1 : nhwc ? q * cout_last + c : c * P + q; };
+    ppg_pack_fc(64 * P, 8, [&](int o, int k) {
+        const int c = 32 * (k / (32 * P)) + k % 32, q = (k % (32 * P)) / 32, ft = feature(c, q);
+        return (o < h1 && ft >= 0) ? w1[(size_t)o * flat + ft] : 0.0f; }, F.f[PPG_FRAG_FC]);
+    for (int i = 0; i < h1; ++i) bias[i] = sp.fc_b[0][i];
+    if (sp.n_fc == 3) {
+        const float *w2 = sp.fc_w[1];
+        ppg_pack_fc(256, 8, [&](int o, int k) { return (o < h2 && k < h1) ? w2[(size_t)o * h1 + k] : 0.0f; }, F.f[PPG_FRAG_FC + 1]);
+        for (int i = 0; i < h2; ++i) bias[256 + i] = sp.fc_b[1][i];
+    }
+    const float *w3 = sp.fc_w[sp.n_fc - 1];
+    const int hl = sp.n_fc == 3 ? h2 : h1;
+    ppg_pack_fc(256, 1, [&](int o, int k) { return (o < n_actions && k < hl) ? w3[(size_t)o * hl + k] : 0.0f; }, F.f[PPG_FRAG_FC + 2]);
+    for (int i = 0; i < n_actions; ++i) bias[512 + i] = sp.fc_b[sp.n_fc - 1][i];
+}
+
 int ppg_policy_create_spec(int32_t device, const ppg_policy_spec *spec, ppg_policy **out) {
     if (!spec || !out) return ppg_policy_fail(nullptr, PPG_EINVAL, "null argument");
     const ppg_policy_spec &sp = *spec;
@@ -1313,112 +1443,58 @@ int ppg_policy_create_spec(int32_t device, const ppg_policy_spec *spec, ppg_poli
         const int rc = ppg_policy_check_spec(sp, true);
         if (rc != PPG_OK) return rc;
     }
-    // the image the convolutions run on: R x R with C channels, or (channels-last) C x R with R channels
     const int hwc = layout == PPG_POLICY_LAYOUT_HWC;
-    const int IH = hwc ? C : R, IW = R, CIN = hwc ? R : C, CB1 = CIN > 8 ? 2 : 1;
-    const int P = IH * IW;
-    const bool direct = sp.n_fc == 1;
+    const int IH = hwc ? C : R, IW = R, CIN = hwc ? R : C, P = IH * IW, K1 = 64 * P;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return ppg_policy_fail(nullptr, PPG_ENODEV, "device %d not available", device);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return ppg_policy_fail(nullptr, PPG_ENODEV, "ppg_policy needs a gfx950 device (MI355X)");
+    ppg_policy_layout L;
+    {
+        const int rc = ppg_policy_layout_of(sp, ppg_pipe_enabled(), L);
+        if (rc != PPG_OK) return rc;
+    }
+    ppg_policy_fragments F;
+    ppg_policy_fragments_of(sp, F);
+    F.f[PPG_FRAG_SLOTS] = L.slot_tab;
     ppg_policy *p = new (std::nothrow) ppg_policy();
     if (!p) return ppg_policy_fail(nullptr, PPG_ENOMEM, "out of host memory");
-    memset(p, 0, sizeof *p);
+    memset(p, 0, sizeof *p);   // (every failure below: ppg_policy_destroy frees what exists by then)
     p->device = device; p->R = R; p->n_actions = n_actions; p->layout = layout; p->cin = CIN; p->obs_channels = C;
-    p->direct = direct ? (sp.n_conv > 3 ? 2 : 1) : 0;
+    p->direct = L.family == 3 ? 1 : L.family;
+    p->pipe = L.family == 3;
     p->nch16 = CIN > 8;
-    const int cout_last = sp.conv_out[sp.n_conv - 1];
-    const int flat = P * cout_last;   // features behind the flatten
+    p->lds_bytes = L.lds_bytes;
+    p->grid = L.wgs_per_cu * prop.multiProcessorCount;
+#ifdef PPG_EXPERIMENTS
+    if (const char *g = getenv("PPG_POLICY_GRID")) p->grid = L.wgs_per_cu == 2 && atoi(g) > 0 ? atoi(g) : p->grid;   // resident workgroups
+#endif
     {   // real multiply-accumulates per observation
         uint64_t m = 0;
         int ci = CIN;
         for (int l = 0; l < sp.n_conv; ++l) { m += (uint64_t)P * sp.conv_out[l] * 9 * ci; ci = sp.conv_out[l]; }
-        int fi = flat;
+        int fi = P * sp.conv_out[sp.n_conv - 1];
         for (int l = 0; l < sp.n_fc; ++l) { m += (uint64_t)fi * sp.fc_out[l]; fi = sp.fc_out[l]; }
         p->macs = m;
     }
-    ppgpol::PolParams &K = p->base;
-    // feature index of (channel c, position q) behind the flatten, or -1 for a padding channel
-    const int flatten = sp.flatten;
-    auto feature = [=](int c, int q) { return c >= cout_last ? -1 : flatten == PPG_POLICY_FLATTEN_NHWC ? q * cout_last + c : c * P + q; };
-    std::vector<uint16_t> f[PPG_POLICY_MAX_CONV + 5];   // conv layers, then up to three linear layers, conv1 in the pipeline's form, its slot table
-    std::vector<float> bias(256 + 256 + 32 + 16, 0.0f); // FC chain: b1, b2, b3; direct: head bias at [512]; the pipeline's conv1 bias at [544]
-    int ci = CIN;
-    for (int l = 0; l < sp.n_conv; ++l) {
-        ppg_pack_conv(sp.conv_w[l], sp.conv_b[l], sp.conv_out[l], ci, l == 0 ? CB1 : l == 1 ? 2 : l == 2 ? 4 : 8, l < 2 ? 1 : 2, f[l]);
-        K.cout_blocks[l] = (sp.conv_out[l] + 7) / 8;
-        ci = sp.conv_out[l];
-    }
-    const int FC0 = PPG_POLICY_MAX_CONV;
-    const int K1 = 64 * P;
-    if (direct) {
-        // head fragments of v_mfma_f32_16x16x32_bf16, [action tile][k-step][lane][8]: lane holds action 16 tile + (lane & 15) and the
-        // features of area F's elements 32 ks + 8 (lane >> 4) + j; F is [position][flat_c channels]
-        const int flat_c = 8 * K.cout_blocks[sp.n_conv - 1], ksteps = (P * flat_c + 31) / 32, head_mt = (n_actions + 15) / 16;
-        K.flat_c = flat_c; K.kflat_steps = ksteps; K.head_mt = head_mt;
-        ppg_pack_head(sp.fc_w[0], n_actions, P, cout_last, flatten == PPG_POLICY_FLATTEN_NHWC, f[FC0]);
-        for (int a = 0; a < n_actions; ++a) bias[512 + a] = sp.fc_b[0][a];
-        {   // K.whw: wavefront w owns k-steps [w per, (w + 1) per), its first 18 ride in registers (ppg_policy_direct.h)
-            const int HFR = 18, per = (ksteps + 3) / 4;
-            f[FC0 + 1].assign((size_t)4 * HFR * 64 * 8, 0);
-            for (int w = 0; w < 4; ++w)
-                for (int i = 0; i < HFR && i < per; ++i) {
-                    const int ks = w * per + i;
-                    if (ks >= ksteps) break;
-                    memcpy(&f[FC0 + 1][((size_t)w * HFR + i) * 64 * 8], &f[FC0][(size_t)ks * 64 * 8], 64 * 8 * 2);
-                }
-        }
-    } else {
-        // FC1: the K order is the scratch slot's [row tile of conv3][position][32 channels]; hidden widths are zero-padded to 256
-        const int h1 = sp.fc_out[0], h2 = sp.n_fc == 3 ? sp.fc_out[1] : 0;
-        const float *w1 = sp.fc_w[0];
-        ppg_pack_fc(K1, 8, [&](int o, int k) {
-            const int c = 32 * (k / (32 * P)) + k % 32, q = (k % (32 * P)) / 32, ft = feature(c, q);
-            return (o < h1 && ft >= 0) ? w1[(size_t)o * flat + ft] : 0.0f; }, f[FC0]);
-        for (int i = 0; i < h1; ++i) bias[i] = sp.fc_b[0][i];
-        if (sp.n_fc == 3) {
-            const float *w2 = sp.fc_w[1];
-            ppg_pack_fc(256, 8, [&](int o, int k) { return (o < h2 && k < h1) ? w2[(size_t)o * h1 + k] : 0.0f; }, f[FC0 + 1]);
-            for (int i = 0; i < h2; ++i) bias[256 + i] = sp.fc_b[1][i];
-        }
-        const float *w3 = sp.fc_w[sp.n_fc - 1];
-        const int hl = sp.n_fc == 3 ? h2 : h1;
-        ppg_pack_fc(256, 1, [&](int o, int k) { return (o < n_actions && k < hl) ? w3[(size_t)o * hl + k] : 0.0f; }, f[FC0 + 2]);
-        for (int i = 0; i < n_actions; ++i) bias[512 + i] = sp.fc_b[sp.n_fc - 1][i];
-        K.n_hidden = sp.n_fc - 1;
-    }
-    if (CIN <= 9) {
-        ppg_pack_conv1x(sp.conv_w[0], sp.conv_out[0], CIN, f[PPG_POLICY_MAX_CONV + 3]);
-        for (int c = 0; c < sp.conv_out[0] && c < 16; ++c) bias[544 + c] = sp.conv_b[0][c];
-    }
-    // (the pipeline's LDS layout decides its slot table: computed here, before the upload, once more below for the parameter block)
-    int pipe_lds_early = 0;
-    const bool want_pipe = direct && ppg_pipe_enabled() && sp.n_conv == 3 && (n_actions + 15) / 16 == 1 && CIN <= 9;
-    if (want_pipe) {
-        ppgpol::PolParams Kt = K;
-        Kt.Wp = IW + 1; Kt.Wp2 = (IH + 2) * (IW + 1) + 1;
-        const int kfs = (P * 8 * ((cout_last + 7) / 8) + 31) / 32;
-        if ((kfs + 3) / 4 <= 18)
-            (void)ppg_pipe_layout(C, R, P, Kt.Wp2 * 8, kfs * 32 + 8, 18 * 32 * 2, Kt, &pipe_lds_early, &f[PPG_POLICY_MAX_CONV + 4]);
-    }
-    const int NF = PPG_POLICY_MAX_CONV + 5;
+    const int NF = PPG_FRAG_N;
     size_t off[NF + 1], total = 0;
-    for (int l = 0; l < NF; ++l) { off[l] = total; total += (f[l].size() * 2 + 255) / 256 * 256; }
-    off[NF] = total; total += bias.size() * 4;
+    for (int l = 0; l < NF; ++l) { off[l] = total; total += (F.f[l].size() * 2 + 255) / 256 * 256; }
+    off[NF] = total; total += F.bias.size() * 4;
     if (hipSetDevice(device) != hipSuccess || hipMalloc(&p->dev_weights, total) != hipSuccess) {
-        delete p;
+        (void)ppg_policy_destroy(p);
         return ppg_policy_fail(nullptr, PPG_EHIP, "hipMalloc of %zu bytes of weights failed", total);
     }
     std::vector<unsigned char> stage(total, 0);
-    for (int l = 0; l < NF; ++l) if (!f[l].empty()) memcpy(stage.data() + off[l], f[l].data(), f[l].size() * 2);
-    memcpy(stage.data() + off[NF], bias.data(), bias.size() * 4);
+    for (int l = 0; l < NF; ++l) if (!F.f[l].empty()) memcpy(stage.data() + off[l], F.f[l].data(), F.f[l].size() * 2);
+    memcpy(stage.data() + off[NF], F.bias.data(), F.bias.size() * 4);
     if (hipMemcpy(p->dev_weights, stage.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(p->dev_weights);
-        delete p;
+        (void)ppg_policy_destroy(p);
         return ppg_policy_fail(nullptr, PPG_EHIP, "upload of the weights failed");
     }
+    ppgpol::PolParams &K = p->base;
+    K = L.K;
 #ifdef PPG_EXPERIMENTS   // ablation builds only (hipcc -DPPG_EXPERIMENTS): skip phases -- the results are then meaningless
     if (const char *dbg = getenv("PPG_POLICY_SKIP")) K.debug_skip = atoi(dbg);
 #endif
@@ -1427,6 +1503,8 @@ int ppg_policy_create_spec(int32_t device, const ppg_policy_spec *spec, ppg_poli
     K.R = R; K.P = P; K.K1 = K1; K.n_actions = n_actions;
     K.IH = IH; K.IW = IW; K.cin = CIN; K.obs_elems = C * R * R;
     K.n_conv = sp.n_conv;
+    for (int l = 0; l < sp.n_conv; ++l) K.cout_blocks[l] = (sp.conv_out[l] + 7) / 8;
+    K.n_hidden = L.family == 0 ? sp.n_fc - 1 : 0;
     // observation element [a][b][c] of the (C,R,R) row: channel-first = (channel a, position b * R + c); channels-last = (position
     // a * R + b, channel c)
     K.c_stride = hwc ? 1 : R * R; K.p_stride = hwc ? R : 1;
@@ -1434,100 +1512,38 @@ int ppg_policy_create_spec(int32_t device, const ppg_policy_spec *spec, ppg_poli
     K.wc1 = (const ppgpol::bf16x8 *)(dw + off[0]); K.wc2 = (const ppgpol::bf16x8 *)(dw + off[1]);
     K.wc3 = (const ppgpol::bf16x8 *)(dw + off[2]);
     for (int l = 3; l < PPG_POLICY_MAX_CONV; ++l) K.wcd[l - 3] = (const ppgpol::bf16x8 *)(dw + off[l]);
-    K.w1 = (const ppgpol::bf16x8 *)(dw + off[FC0]); K.w2 = (const ppgpol::bf16x8 *)(dw + off[FC0 + 1]); K.w3 = (const ppgpol::bf16x8 *)(dw + off[FC0 + 2]);
+    K.w1 = (const ppgpol::bf16x8 *)(dw + off[PPG_FRAG_FC]); K.w2 = (const ppgpol::bf16x8 *)(dw + off[PPG_FRAG_FC + 1]); K.w3 = (const ppgpol::bf16x8 *)(dw + off[PPG_FRAG_FC + 2]);
     K.wh = K.w1; K.whw = K.w2;
     const float *db = (const float *)(dw + off[NF]);
     K.bc1 = K.bc2 = K.bc3 = nullptr;   // (the convolutions' biases ride in their fragments)
     K.b1 = db; K.b2 = db + 256; K.b3 = db + 512; K.bh = db + 512;
-    K.wc1x = (const ppgpol::bf16x8 *)(dw + off[PPG_POLICY_MAX_CONV + 3]); K.bc1x = db + 544;
-    K.slot_tab = (const uint16_t *)(dw + off[PPG_POLICY_MAX_CONV + 4]);
-    p->grid = 2 * prop.multiProcessorCount;
-#ifdef PPG_EXPERIMENTS
-    if (const char *g = getenv("PPG_POLICY_GRID")) p->grid = atoi(g) > 0 ? atoi(g) : p->grid;   // resident workgroups
-#endif
-    if (direct) {
-        // LDS region of a sample: X (4 blocks) | Y (2 blocks) | F | [D0 | D1] -- padded pitch W + 1 (ppg_policy_direct.h)
-        K.Wp = IW + 1; K.Wp2 = (IH + 2) * (IW + 1) + 1;
-        const int blk = K.Wp2 * 8, f_elems = K.kflat_steps * 32 + 8;   // (+ 8: consecutive samples' fragments fall into different banks)
-        K.off_x = 0; K.off_y = 4 * blk; K.off_f = 6 * blk; K.off_d0 = K.off_f + f_elems; K.off_d1 = K.off_d0 + 8 * blk;
-        K.sample_stride = K.off_f + f_elems + (sp.n_conv > 3 ? 8 * blk : 0) + (sp.n_conv > 4 ? 8 * blk : 0);
-        const int tail_slack = 18 * 32 * 2;   // bytes behind the last sample's region: the head's unconditional fragment reads end there
-        // the two-role pipeline (ppg_policy_pipe.h): three convolutions, up to 16 actions, a wavefront's quarter of the head's k-steps in 18
-        // fragments; region of a sample: X0 | X1 (4 blocks each) | Y (2 blocks) | F0 | F1
-        if (ppg_pipe_enabled() && sp.n_conv == 3 && K.head_mt == 1 && (K.kflat_steps + 3) / 4 <= 18 && CIN <= 9) {   // (CIN: Conv1X)
-            int pipe_lds = 0;
-            if (ppg_pipe_layout(C, R, P, blk, f_elems, tail_slack, K, &pipe_lds)) {
-                p->pipe = 1;
-                p->grid = prop.multiProcessorCount;
-                p->lds_bytes = pipe_lds;
-                if (ppg_policy_matches_description(p, spec) != PPG_OK) { (void)ppg_policy_destroy(p); return PPG_EHIP; }
-                *out = p;
-                return PPG_OK;
-            }
-        }
-        const int fixed = ppgpol::TILE * 16 + K.head_mt * 4096 + 4096 + tail_slack;   // table, partial logits, dconv's dummy slots
-        const bool w1 = PPG_DIRECT_W1;   // one workgroup per CU with all of its LDS (ppg_policy_direct.h)
-        int st_max = ((w1 ? 160 : 80) * 1024 - fixed) / (K.sample_stride * 2);
-        if (st_max > 16) st_max = 16;                // (the head's 16 sample columns)
-        while (st_max > 1 && st_max * P > (w1 ? 512 : 256)) --st_max;   // a thread stages at most two / one positions
-        if (w1) p->grid = prop.multiProcessorCount;
-        if (st_max < 1) {
-            (void)hipFree(p->dev_weights);
-            delete p;
-            return ppg_policy_fail(nullptr, PPG_EINVAL, "a %d x %d image with %d convolutions needs %d bytes of LDS per sample: too large", IH, IW, sp.n_conv, K.sample_stride * 2);
-        }
-        // samples per sub-group: the most samples per round of position tiles (four wavefronts take a tile each)
-        int st = st_max;
-        double best = 0.0;
-        for (int c = st_max; c >= 1; --c) {
-            const int tiles = (c * P + 31) / 32, rounds = (tiles + 3) / 4;
-            const double score = (double)c / rounds;
-            if (score > best * 1.0001) { best = score; st = c; }
-        }
-        K.ST = st;
-        K.range_tile = st * (ppgpol::TILE / st);   // whole sub-groups per tile
-        p->lds_bytes = fixed + st * K.sample_stride * 2;
+    K.wc1x = (const ppgpol::bf16x8 *)(dw + off[PPG_FRAG_CONV1X]); K.bc1x = db + 544;
+    K.slot_tab = (const uint16_t *)(dw + off[PPG_FRAG_SLOTS]);
+    // the family's scratch (the pipeline has none)
+    if (L.family == 1 || L.family == 2) {
         const size_t lgs_bytes = (size_t)p->grid * ppgpol::TILE * 16 * K.head_mt * 4;
         if (hipMalloc((void **)&p->lgs, lgs_bytes) != hipSuccess || hipMemset(p->lgs, 0, lgs_bytes) != hipSuccess) {
-            (void)hipFree(p->dev_weights);
-            delete p;
+            (void)ppg_policy_destroy(p);
             return ppg_policy_fail(nullptr, PPG_EHIP, "hipMalloc of %zu bytes of scratch failed", lgs_bytes);
         }
         K.lgs = p->lgs;
-        if (ppg_policy_matches_description(p, spec) != PPG_OK) { (void)ppg_policy_destroy(p); return PPG_EHIP; }
-        *out = p;
-        return PPG_OK;
-    }
-    K.Wp = IW + 2; K.Wp2 = (IH + 2) * (IW + 2);
-    // LDS: tile table + max(activation images of ST samples, H); ST as large as 2 workgroups per CU (80 KB each) allow
-    const int per_sample = 6 * K.Wp2 * 8 * 2;                       // X (4 blocks) + Y (2 blocks), bytes
-    const int h_bytes = ppgpol::TILE * ppgpol::HSTRIDE * 2;
-    int st = (78 * 1024 - ppgpol::TILE * 16) / per_sample;
-    if (st < 1) st = 1;
-    if (st > 16) st = 16;
-    while (st > 1 && st * P > 512) --st;   // the staging of a sub-group gives every thread at most two positions
-    K.ST = st;
-    const int img = st * per_sample, fc1_stage = 3 * ppgpol::FC1_BUF;
-    int overlay = img > h_bytes ? img : h_bytes;
-    if (fc1_stage > overlay) overlay = fc1_stage;
-    p->lds_bytes = ppgpol::TILE * 16 + overlay;
-    const size_t xg_bytes = (size_t)p->grid * ppgpol::TILE * K1 * 2;
-    // the scratch slots: 512 concurrent sequential streams, written by conv3 and read back by FC1 -- on spread physical pages like the
-    // env's observation tensors where the virtual-memory calls work (-DPPG_POLICY_XG_SPREAD=0: A/B builds)
+    } else if (L.family == 0) {
+        const size_t xg_bytes = (size_t)p->grid * ppgpol::TILE * K1 * 2;
+        // the scratch slots: 512 concurrent sequential streams, written by conv3 and read back by FC1 -- on spread physical pages like the
+        // env's observation tensors where the virtual-memory calls work (-DPPG_POLICY_XG_SPREAD=0: A/B builds)
 #ifndef PPG_POLICY_XG_SPREAD
 #define PPG_POLICY_XG_SPREAD 16
 #endif
-    const int xg_spread = PPG_POLICY_XG_SPREAD;
-    void *xg_ptr = nullptr;
-    p->xg_is_spread = xg_spread > 1 && ppg_alloc_spread(device, (uint64_t)xg_bytes, xg_spread, 0x5850u + (uint64_t)R, &xg_ptr) == PPG_OK;
-    if (p->xg_is_spread) p->xg = (__bf16 *)xg_ptr;
-    if ((!p->xg_is_spread && hipMalloc((void **)&p->xg, xg_bytes) != hipSuccess) || hipMemset(p->xg, 0, xg_bytes) != hipSuccess) {
-        (void)hipFree(p->dev_weights);
-        delete p;
-        return ppg_policy_fail(nullptr, PPG_EHIP, "hipMalloc of %zu bytes of scratch failed", xg_bytes);
+        const int xg_spread = PPG_POLICY_XG_SPREAD;
+        void *xg_ptr = nullptr;
+        p->xg_is_spread = xg_spread > 1 && ppg_alloc_spread(device, (uint64_t)xg_bytes, xg_spread, 0x5850u + (uint64_t)R, &xg_ptr) == PPG_OK;
+        if (p->xg_is_spread) p->xg = (__bf16 *)xg_ptr;
+        if ((!p->xg_is_spread && hipMalloc((void **)&p->xg, xg_bytes) != hipSuccess) || hipMemset(p->xg, 0, xg_bytes) != hipSuccess) {
+            (void)ppg_policy_destroy(p);
+            return ppg_policy_fail(nullptr, PPG_EHIP, "hipMalloc of %zu bytes of scratch failed", xg_bytes);
+        }
+        K.xg = p->xg;
     }
-    K.xg = p->xg;
-    if (ppg_policy_matches_description(p, spec) != PPG_OK) { (void)ppg_policy_destroy(p); return PPG_EHIP; }
     *out = p;
     return PPG_OK;
 }
@@ -1537,32 +1553,30 @@ int ppg_policy_pack(const ppg_policy_spec *spec, int32_t what, uint16_t *out, ui
     const ppg_policy_spec &sp = *spec;
     const int rc = ppg_policy_check_spec(sp, true);
     if (rc != PPG_OK) return rc;
-    const int hwc = sp.layout == PPG_POLICY_LAYOUT_HWC;
-    const int IH = hwc ? sp.obs_channels : sp.obs_range, IW = sp.obs_range, CIN = hwc ? sp.obs_range : sp.obs_channels, P = IH * IW;
-    std::vector<uint16_t> f;
-    if (what >= 0 && what < sp.n_conv) {
-        int ci = CIN;
-        for (int l = 0; l < what; ++l) ci = sp.conv_out[l];
-        ppg_pack_conv(sp.conv_w[what], sp.conv_b[what], sp.conv_out[what], ci, what == 0 ? (CIN > 8 ? 2 : 1) : what == 1 ? 2 : what == 2 ? 4 : 8,
-                      what < 2 ? 1 : 2, f);
-    } else if (what == PPG_POLICY_PACK_CONV1X) {
-        if (CIN > 9) return ppg_policy_fail(nullptr, PPG_EINVAL, "the pipeline's first convolution takes up to nine input channels (found %d)", CIN);
-        ppg_pack_conv1x(sp.conv_w[0], sp.conv_out[0], CIN, f);
-    } else if (what == PPG_POLICY_PACK_SLOTS) {
-        ppgpol::PolParams K;
-        memset(&K, 0, sizeof K);
-        const int cb = (sp.conv_out[sp.n_conv - 1] + 7) / 8, kfs = (P * 8 * cb + 31) / 32;
-        K.Wp = IW + 1; K.Wp2 = (IH + 2) * (IW + 1) + 1;
-        int lds = 0;
-        if (!(sp.n_fc == 1 && sp.n_conv == 3 && (sp.n_actions + 15) / 16 == 1 && (kfs + 3) / 4 <= 18 && CIN <= 9 &&
-              ppg_pipe_layout(sp.obs_channels, sp.obs_range, P, K.Wp2 * 8, kfs * 32 + 8, 18 * 32 * 2, K, &lds, &f)))
+    const int CIN = sp.layout == PPG_POLICY_LAYOUT_HWC ? sp.obs_range : sp.obs_channels;
+    ppg_policy_fragments F;
+    int which;
+    if (what == PPG_POLICY_PACK_SLOTS) {   // (whatever PPG_POLICY_PIPE says)
+        ppg_policy_layout L;
+        if (ppg_policy_layout_of(sp, true, L) != PPG_OK || L.family != 3)
             return ppg_policy_fail(nullptr, PPG_EINVAL, "PPG_POLICY_PACK_SLOTS: not a network of the two-role pipeline");
-    } else if (what == PPG_POLICY_PACK_HEAD) {
-        if (sp.n_fc != 1) return ppg_policy_fail(nullptr, PPG_EINVAL, "PPG_POLICY_PACK_HEAD: the network has hidden head layers");
-        ppg_pack_head(sp.fc_w[0], sp.n_actions, P, sp.conv_out[sp.n_conv - 1], sp.flatten == PPG_POLICY_FLATTEN_NHWC, f);
+        which = PPG_FRAG_SLOTS;
+        F.f[which].swap(L.slot_tab);
     } else {
-        return ppg_policy_fail(nullptr, PPG_EINVAL, "ppg_policy_pack: unknown layer %d", what);
+        if (what >= 0 && what < sp.n_conv) {
+            which = what;
+        } else if (what == PPG_POLICY_PACK_CONV1X) {
+            if (CIN > 9) return ppg_policy_fail(nullptr, PPG_EINVAL, "the pipeline's first convolution takes up to nine input channels (found %d)", CIN);
+            which = PPG_FRAG_CONV1X;
+        } else if (what == PPG_POLICY_PACK_HEAD) {
+            if (sp.n_fc != 1) return ppg_policy_fail(nullptr, PPG_EINVAL, "PPG_POLICY_PACK_HEAD: the network has hidden head layers");
+            which = PPG_FRAG_FC;
+        } else {
+            return ppg_policy_fail(nullptr, PPG_EINVAL, "ppg_policy_pack: unknown layer %d", what);
+        }
+        ppg_policy_fragments_of(sp, F);
     }
+    const std::vector<uint16_t> &f = F.f[which];
     *n_words = f.size();
     if (out && capacity >= f.size()) memcpy(out, f.data(), f.size() * 2);
     return PPG_OK;
@@ -1570,50 +1584,13 @@ int ppg_policy_pack(const ppg_policy_spec *spec, int32_t what, uint16_t *out, ui
 
 int ppg_policy_describe(const ppg_policy_spec *spec, int32_t *out, int32_t n) {
     if (!spec || !out || n < 1) return PPG_EINVAL;
-    const ppg_policy_spec &sp = *spec;
-    const int R = sp.obs_range, C = sp.obs_channels;
-    if (ppg_policy_check_spec(sp, false) != PPG_OK) return PPG_EINVAL;
-    const int hwc = sp.layout == PPG_POLICY_LAYOUT_HWC;
-    const int IH = hwc ? C : R, IW = R, P = IH * IW;
-    int32_t v[12] = {0, 0, 0, 256, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (sp.n_fc > 1) {   // FC chain: tile table + max(images of ST samples, H, FC1 staging); two workgroups per CU
-        const int per_sample = 6 * (IH + 2) * (IW + 2) * 8 * 2;
-        int st = (78 * 1024 - ppgpol::TILE * 16) / per_sample;
-        st = st < 1 ? 1 : st > 16 ? 16 : st;
-        while (st > 1 && st * P > 512) --st;
-        int overlay = st * per_sample;
-        if (ppgpol::TILE * ppgpol::HSTRIDE * 2 > overlay) overlay = ppgpol::TILE * ppgpol::HSTRIDE * 2;
-        if (3 * ppgpol::FC1_BUF > overlay) overlay = 3 * ppgpol::FC1_BUF;
-        v[1] = st; v[2] = ppgpol::TILE * 16 + overlay;
-    } else {
-        ppgpol::PolParams K;
-        memset(&K, 0, sizeof K);
-        const int cout_last_blocks = (sp.conv_out[sp.n_conv - 1] + 7) / 8;
-        K.flat_c = 8 * cout_last_blocks; K.kflat_steps = (P * K.flat_c + 31) / 32; K.head_mt = (sp.n_actions + 15) / 16;
-        K.Wp = IW + 1; K.Wp2 = (IH + 2) * (IW + 1) + 1;
-        const int blk = K.Wp2 * 8, f_elems = K.kflat_steps * 32 + 8, tail_slack = 18 * 32 * 2;
-        int lds = 0;
-        if (ppg_pipe_enabled() && sp.n_conv == 3 && K.head_mt == 1 && (K.kflat_steps + 3) / 4 <= 18 && (hwc ? R : C) <= 9 &&
-            ppg_pipe_layout(C, R, P, blk, f_elems, tail_slack, K, &lds)) {
-            v[0] = 3; v[1] = K.ST; v[2] = lds; v[3] = 512; v[4] = K.range_tile; v[5] = K.sample_stride * 2; v[6] = K.pipe_ni; v[7] = K.pipe_slots;
-            v[8] = K.pipe_red; v[9] = K.pipe_raw; v[10] = K.pipe_img; v[11] = K.pipe_img - 1024 - K.pipe_raw;
-        } else {
-            const int stride = 6 * blk + f_elems + (sp.n_conv > 3 ? 8 * blk : 0) + (sp.n_conv > 4 ? 8 * blk : 0);
-            const int fixed = ppgpol::TILE * 16 + K.head_mt * 4096 + 4096 + tail_slack;
-            const bool w1 = PPG_DIRECT_W1;
-            int st_max = ((w1 ? 160 : 80) * 1024 - fixed) / (stride * 2);
-            if (st_max > 16) st_max = 16;
-            while (st_max > 1 && st_max * P > (w1 ? 512 : 256)) --st_max;
-            if (st_max < 1) return PPG_EINVAL;
-            int st = st_max;
-            double best = 0.0;
-            for (int c = st_max; c >= 1; --c) {
-                const int tiles = (c * P + 31) / 32, rounds = (tiles + 3) / 4;
-                const double score = (double)c / rounds;
-                if (score > best * 1.0001) { best = score; st = c; }
-            }
-            v[0] = sp.n_conv > 3 ? 2 : 1; v[1] = st; v[2] = fixed + st * stride * 2;
-        }
+    ppg_policy_layout L;
+    if (ppg_policy_check_spec(*spec, false) != PPG_OK || ppg_policy_layout_of(*spec, ppg_pipe_enabled(), L) != PPG_OK) return PPG_EINVAL;
+    const ppgpol::PolParams &K = L.K;
+    int32_t v[12] = {L.family, K.ST, L.lds_bytes, L.threads, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (L.family == 3) {   // the pipeline's areas: samples of table, bytes of a sample's region, row loads, byte offsets, bytes of the row area
+        v[4] = K.range_tile; v[5] = K.sample_stride * 2; v[6] = K.pipe_ni; v[7] = K.pipe_slots;
+        v[8] = K.pipe_red; v[9] = K.pipe_raw; v[10] = K.pipe_img; v[11] = K.pipe_img - 1024 - K.pipe_raw;
     }
     for (int i = 0; i < n && i < 12; ++i) out[i] = v[i];
     return PPG_OK;
@@ -1680,6 +1657,47 @@ static int ppg_pipe_debug_check(ppg_policy *p) {
                                st[0], st[1], st[2], st[3], st[4]);
     return PPG_OK;
 }
+#endif
+
+#if defined(PPG_EXPERIMENTS) || defined(PPG_DIRECT_PROFILE)
+// diagnostic builds: a device buffer that ONE launch of a kind fills with stamps -- allocated (zeroed) at the first launch with $path_env
+// set, handed to launch number $run_env (default 300), and after that launch written to the file "$path_env.<suffix>"
+struct ppg_policy_dump {
+    const char *path_env, *run_env;
+    unsigned long long *buf;
+    int runs;
+    bool armed;   // the launch being prepared is the one
+};
+static int ppg_policy_dump_arm(ppg_policy *p, ppg_policy_dump &d, size_t bytes, void **slot) {   // *slot: the parameter block's pointer
+    const char *path = getenv(d.path_env), *at = getenv(d.run_env);
+    if (path && !d.buf) {
+        PPG_POL_TRY(p, hipMalloc((void **)&d.buf, bytes));
+        PPG_POL_TRY(p, hipMemset(d.buf, 0, bytes));
+        PPG_POL_TRY(p, hipDeviceSynchronize());
+    }
+    d.armed = path && ++d.runs == (at ? atoi(at) : 300);
+    *slot = d.armed ? d.buf : nullptr;
+    return PPG_OK;
+}
+static int ppg_policy_dump_write(ppg_policy *p, const ppg_policy_dump &d, size_t bytes, const char *suffix) {
+    if (!d.buf) return PPG_OK;
+    PPG_POL_TRY(p, hipDeviceSynchronize());
+    std::vector<unsigned long long> host(bytes / 8);
+    PPG_POL_TRY(p, hipMemcpy(host.data(), d.buf, bytes, hipMemcpyDeviceToHost));
+    char name[512];
+    snprintf(name, sizeof name, "%s.%s", getenv(d.path_env), suffix);
+    if (FILE *f = fopen(name, "wb")) { fwrite(host.data(), 8, host.size(), f); fclose(f); }
+    return PPG_OK;
+}
+#endif
+#ifdef PPG_EXPERIMENTS   // PPG_POLICY_TIMELINE=<file prefix>: per-tile phase stamps of launch number PPG_POLICY_TIMELINE_RUN of each species -> <prefix>.{pred,prey}
+static ppg_policy_dump g_ppg_timeline[2] = {{"PPG_POLICY_TIMELINE", "PPG_POLICY_TIMELINE_RUN"}, {"PPG_POLICY_TIMELINE", "PPG_POLICY_TIMELINE_RUN"}};
+#endif
+#ifdef PPG_DIRECT_PROFILE   // per-wavefront phase cycles of launch number PPG_DIRECT_PROFILE_RUN -> $PPG_DIRECT_PROFILE_FILE.{pred,prey,fused}
+static ppg_policy_dump g_ppg_direct_profile[3] = {{"PPG_DIRECT_PROFILE_FILE", "PPG_DIRECT_PROFILE_RUN"}, {"PPG_DIRECT_PROFILE_FILE", "PPG_DIRECT_PROFILE_RUN"},
+                                                  {"PPG_DIRECT_PROFILE_FILE", "PPG_DIRECT_PROFILE_RUN"}};
+// [workgroup][wavefront][16] (the pipeline kernels have eight wavefronts, the others use the first half)
+static size_t ppg_direct_profile_bytes(const ppg_policy *p) { return (size_t)p->grid * 8 * 16 * 8; }
 #endif
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the process-global kernel symbol, not of a policy: two live policies that
@@ -1749,16 +1767,11 @@ static int ppg_policy_run(ppg_policy *p, int species, ppg_handle *const *handles
     ppgpol::PolParams K;
     ppgpol::PlanParams L;
     int total = 0;
-    {
-        const int rc = ppg_policy_fill(p, species, handles, n, actions, flags, seed, logits, K, L, total);
-        if (rc != PPG_OK) return rc;
-    }
+    int rc = ppg_policy_fill(p, species, handles, n, actions, flags, seed, logits, K, L, total);
+    if (rc != PPG_OK) return rc;
     if (K.obs_f32 == 3)
         return ppg_policy_fail(p, PPG_EINVAL, "observation rows in the cell layout (obs_dtype 3) need the one-launch form: both species' pipeline policies in one ppg_policy_act call");
-    {
-        const int rc = ppg_policy_ensure_plan(p, total, K.cap);
-        if (rc != PPG_OK) return rc;
-    }
+    if ((rc = ppg_policy_ensure_plan(p, total, K.cap)) != PPG_OK) return rc;
     K.plan = L.plan = p->plan;
     K.tile_env = L.tile_env = p->plan + ppgpol::PLAN_HDR + total;
     L.slots = p->grid;
@@ -1769,24 +1782,12 @@ static int ppg_policy_run(ppg_policy *p, int species, ppg_handle *const *handles
         const int v = atoi(f);
         if (v == 32 || v == 64 || v == 96 || v == 128) L.force_ts = v;
     }
-#endif
-#ifdef PPG_EXPERIMENTS   // PPG_POLICY_TIMELINE=<file prefix>: per-tile phase stamps of launch number PPG_POLICY_TIMELINE_RUN (default 300) of each species
-    static int tl_runs[2] = {0, 0};
-    static unsigned long long *tl_buf[2] = {nullptr, nullptr};
-    const char *tl_path = getenv("PPG_POLICY_TIMELINE");
-    const int tl_at = getenv("PPG_POLICY_TIMELINE_RUN") ? atoi(getenv("PPG_POLICY_TIMELINE_RUN")) : 300;
-    const size_t tl_tiles = ((size_t)total * K.cap + 31) / 32 + 1;
-    if (tl_path && !tl_buf[species]) {
-        PPG_POL_TRY(p, hipMalloc((void **)&tl_buf[species], tl_tiles * 512));
-        PPG_POL_TRY(p, hipMemset(tl_buf[species], 0, tl_tiles * 512));
-        PPG_POL_TRY(p, hipDeviceSynchronize());
-    }
-    const bool tl_now = tl_path && ++tl_runs[species] == tl_at;
-    K.timeline = tl_now ? tl_buf[species] : nullptr;
+    const size_t tl_bytes = (((size_t)total * K.cap + 31) / 32 + 1) * 512;   // [tile][64] stamps
+    if ((rc = ppg_policy_dump_arm(p, g_ppg_timeline[species], tl_bytes, (void **)&K.timeline)) != PPG_OK) return rc;
 #endif
     if (also_plan_for) {   // the other species' plan in the same launch: same envs, its row-count word, its buffers, its grid
         ppg_policy *o = also_plan_for;
-        const int rc = ppg_policy_ensure_plan(o, total, species ? h0->base.cap_pred : h0->base.cap_prey);
+        rc = ppg_policy_ensure_plan(o, total, species ? h0->base.cap_pred : h0->base.cap_prey);
         if (rc != PPG_OK) { memcpy(p->err, o->err, sizeof p->err); return rc; }
         ppgpol::PlanParams L2 = L;
         L2.word = species ? PPG_ENV_N_PRED_ROWS : PPG_ENV_N_PREY_ROWS;
@@ -1805,19 +1806,8 @@ static int ppg_policy_run(ppg_policy *p, int species, ppg_handle *const *handles
                               {ppgpol::ppg_policy_forward_hwc8_f64, ppgpol::ppg_policy_forward_hwc8_f32, ppgpol::ppg_policy_forward_hwc8_bf16},
                               {ppgpol::ppg_policy_forward_hwc16_f64, ppgpol::ppg_policy_forward_hwc16_f32, ppgpol::ppg_policy_forward_hwc16_bf16}};
     const int dt = K.obs_f32 == 2 ? 2 : K.obs_f32 ? 1 : 0;
-#ifdef PPG_DIRECT_PROFILE   // diagnostic build: per-wavefront phase cycles of launch number PPG_DIRECT_PROFILE_RUN (default 300) -> $PPG_DIRECT_PROFILE_FILE.{pred,prey}
-    static int dp_runs[2] = {0, 0};
-    static unsigned long long *dp_buf[2] = {nullptr, nullptr};
-    const char *dp_path = getenv("PPG_DIRECT_PROFILE_FILE");
-    const int dp_at = getenv("PPG_DIRECT_PROFILE_RUN") ? atoi(getenv("PPG_DIRECT_PROFILE_RUN")) : 300;
-    const size_t dp_bytes = (size_t)p->grid * 8 * 16 * 8;   // (the pipeline kernels have eight wavefronts, the others use the first half)
-    if (p->direct && dp_path && !dp_buf[species]) {
-        PPG_POL_TRY(p, hipMalloc((void **)&dp_buf[species], dp_bytes));
-        PPG_POL_TRY(p, hipMemset(dp_buf[species], 0, dp_bytes));
-        PPG_POL_TRY(p, hipDeviceSynchronize());
-    }
-    const bool dp_now = p->direct && dp_path && ++dp_runs[species] == dp_at;
-    K.xg = dp_now ? (__bf16 *)dp_buf[species] : nullptr;
+#ifdef PPG_DIRECT_PROFILE   // (the FC chain's kernels write no profile: K.xg is their scratch)
+    if (p->direct && (rc = ppg_policy_dump_arm(p, g_ppg_direct_profile[species], ppg_direct_profile_bytes(p), (void **)&K.xg)) != PPG_OK) return rc;
 #endif
     if (p->direct) {
         const fwd_fn dir[4][3] = {{ppgpol::ppg_policy_direct8_f64, ppgpol::ppg_policy_direct8_f32, ppgpol::ppg_policy_direct8_bf16},
@@ -1827,47 +1817,28 @@ static int ppg_policy_run(ppg_policy *p, int species, ppg_handle *const *handles
         const fwd_fn pipe[2][3] = {{ppgpol::ppg_policy_pipe8_f64, ppgpol::ppg_policy_pipe8_f32, ppgpol::ppg_policy_pipe8_bf16},
                                    {ppgpol::ppg_policy_pipe16_f64, ppgpol::ppg_policy_pipe16_f32, ppgpol::ppg_policy_pipe16_bf16}};
         const fwd_fn fn = p->pipe ? pipe[p->nch16 ? 1 : 0][dt] : dir[(p->direct == 2 ? 2 : 0) + (p->nch16 ? 1 : 0)][dt];
-        int rc = ppg_policy_reserve_lds(p, (const void *)fn, p->lds_bytes);
-        if (rc != PPG_OK) return rc;
+        if ((rc = ppg_policy_reserve_lds(p, (const void *)fn, p->lds_bytes)) != PPG_OK) return rc;
 #ifdef PPG_PIPE_DEBUG
-        rc = ppg_pipe_debug_arm(p);
-        if (rc != PPG_OK) return rc;
+        if ((rc = ppg_pipe_debug_arm(p)) != PPG_OK) return rc;
 #endif
         hipLaunchKernelGGL(fn, dim3((unsigned)p->grid), dim3(p->pipe ? 512 : 256), (size_t)p->lds_bytes, (hipStream_t)stream, K);
 #ifdef PPG_PIPE_DEBUG
         PPG_POL_TRY(p, hipGetLastError());
-        rc = ppg_pipe_debug_check(p);
-        if (rc != PPG_OK) return rc;
+        if ((rc = ppg_pipe_debug_check(p)) != PPG_OK) return rc;
 #endif
     } else {
         const int variant = p->layout == PPG_POLICY_LAYOUT_HWC ? (p->cin > 8 ? 2 : 1) : 0;
-        const int rc = ppg_policy_reserve_lds(p, (const void *)fwd[variant][dt], p->lds_bytes);
-        if (rc != PPG_OK) return rc;
+        if ((rc = ppg_policy_reserve_lds(p, (const void *)fwd[variant][dt], p->lds_bytes)) != PPG_OK) return rc;
         hipLaunchKernelGGL(fwd[variant][dt], dim3((unsigned)p->grid), dim3(256), (size_t)p->lds_bytes, (hipStream_t)stream, K);
     }
     PPG_POL_TRY(p, hipGetLastError());
 #ifdef PPG_DIRECT_PROFILE
-    if (dp_now) {
-        PPG_POL_TRY(p, hipDeviceSynchronize());
-        std::vector<unsigned long long> host(dp_bytes / 8);
-        PPG_POL_TRY(p, hipMemcpy(host.data(), dp_buf[species], dp_bytes, hipMemcpyDeviceToHost));
-        char name[512];
-        snprintf(name, sizeof name, "%s.%s", dp_path, species ? "prey" : "pred");
-        if (FILE *f = fopen(name, "wb")) { fwrite(host.data(), 8, host.size(), f); fclose(f); }
-    }
+    if (p->direct && g_ppg_direct_profile[species].armed)
+        if ((rc = ppg_policy_dump_write(p, g_ppg_direct_profile[species], ppg_direct_profile_bytes(p), species ? "prey" : "pred")) != PPG_OK) return rc;
 #endif
 #ifdef PPG_EXPERIMENTS
-    if (tl_now && species == 0) {   // (the predators' launch is the second of a step: both species' stamps are complete after a device sync)
-        PPG_POL_TRY(p, hipDeviceSynchronize());
-        for (int sp = 0; sp < 2; ++sp) {
-            if (!tl_buf[sp]) continue;
-            std::vector<unsigned long long> host(tl_tiles * 64);
-            PPG_POL_TRY(p, hipMemcpy(host.data(), tl_buf[sp], tl_tiles * 512, hipMemcpyDeviceToHost));
-            char name[512];
-            snprintf(name, sizeof name, "%s.%s", tl_path, sp ? "prey" : "pred");
-            if (FILE *f = fopen(name, "wb")) { fwrite(host.data(), 8, host.size(), f); fclose(f); }
-        }
-    }
+    for (int sp = 0; sp < 2 && species == 0 && g_ppg_timeline[0].armed; ++sp)   // (the predators' launch is the second of a step: it writes both species' stamps)
+        if ((rc = ppg_policy_dump_write(p, g_ppg_timeline[sp], tl_bytes, sp ? "prey" : "pred")) != PPG_OK) return rc;
 #endif
     return PPG_OK;
 }
@@ -1892,9 +1863,9 @@ static int ppg_policy_run_fused(ppg_policy *pred, ppg_policy *prey, ppg_handle *
     ppgpol::PlanParams L;
     int total_q = 0, total_p = 0;
     int rc = ppg_policy_fill(prey, 1, handles, n, actions, flags, seed, logits_prey, K2.q, L, total_q);
-    if (rc != PPG_OK) { memcpy(g_ppg_policy_error, prey->err, sizeof g_ppg_policy_error); return rc; }
+    if (rc != PPG_OK) return ppg_policy_mirror(prey, rc);
     rc = ppg_policy_fill(pred, 0, handles, n, actions, flags, seed, logits_pred, K2.p, L, total_p);
-    if (rc != PPG_OK) { memcpy(g_ppg_policy_error, pred->err, sizeof g_ppg_policy_error); return rc; }
+    if (rc != PPG_OK) return ppg_policy_mirror(pred, rc);
     const int lds = prey->lds_bytes > pred->lds_bytes ? prey->lds_bytes : pred->lds_bytes;
     const int img = K2.q.pipe_img > K2.p.pipe_img ? K2.q.pipe_img : K2.p.pipe_img;
     K2.scratch_off = (img + 15) / 16 * 16;
@@ -1914,41 +1885,21 @@ static int ppg_policy_run_fused(ppg_policy *pred, ppg_policy *prey, ppg_handle *
          {ppgpol::ppg_policy_pipe2_16_16_f64, ppgpol::ppg_policy_pipe2_16_16_f32, ppgpol::ppg_policy_pipe2_16_16_bf16}}};
     const int dt = K2.q.obs_f32 == 2 ? 2 : K2.q.obs_f32 ? 1 : 0;
     const fused_fn f = fn[prey->nch16 ? 1 : 0][pred->nch16 ? 1 : 0][dt];
-#ifdef PPG_DIRECT_PROFILE   // diagnostic build: per-wavefront phase cycles of launch number PPG_DIRECT_PROFILE_RUN (default 300) -> $PPG_DIRECT_PROFILE_FILE.fused
-    static int dp_runs = 0;
-    static unsigned long long *dp_buf = nullptr;
-    const char *dp_path = getenv("PPG_DIRECT_PROFILE_FILE");
-    const int dp_at = getenv("PPG_DIRECT_PROFILE_RUN") ? atoi(getenv("PPG_DIRECT_PROFILE_RUN")) : 300;
-    const size_t dp_bytes = (size_t)prey->grid * 8 * 16 * 8;   // (eight wavefronts per workgroup, sixteen words each)
-    if (dp_path && !dp_buf) {
-        PPG_POL_TRY(prey, hipMalloc((void **)&dp_buf, dp_bytes));
-        PPG_POL_TRY(prey, hipMemset(dp_buf, 0, dp_bytes));
-        PPG_POL_TRY(prey, hipDeviceSynchronize());
-    }
-    const bool dp_now = dp_path && ++dp_runs == dp_at;
-    K2.q.xg = K2.p.xg = dp_now ? (__bf16 *)dp_buf : nullptr;
+#ifdef PPG_DIRECT_PROFILE
+    if ((rc = ppg_policy_dump_arm(prey, g_ppg_direct_profile[2], ppg_direct_profile_bytes(prey), (void **)&K2.q.xg)) != PPG_OK) return rc;
+    K2.p.xg = K2.q.xg;
 #endif
-    rc = ppg_policy_reserve_lds(prey, (const void *)f, lds);
-    if (rc != PPG_OK) { memcpy(g_ppg_policy_error, prey->err, sizeof g_ppg_policy_error); return rc; }
+    if ((rc = ppg_policy_reserve_lds(prey, (const void *)f, lds)) != PPG_OK) return ppg_policy_mirror(prey, rc);
 #ifdef PPG_PIPE_DEBUG
-    rc = ppg_pipe_debug_arm(prey);
-    if (rc != PPG_OK) { memcpy(g_ppg_policy_error, prey->err, sizeof g_ppg_policy_error); return rc; }
+    if ((rc = ppg_pipe_debug_arm(prey)) != PPG_OK) return ppg_policy_mirror(prey, rc);
 #endif
     hipLaunchKernelGGL(f, dim3((unsigned)prey->grid), dim3(512), (size_t)lds, (hipStream_t)stream, K2);
     PPG_POL_TRY(prey, hipGetLastError());
 #ifdef PPG_PIPE_DEBUG
-    rc = ppg_pipe_debug_check(prey);
-    if (rc != PPG_OK) { memcpy(g_ppg_policy_error, prey->err, sizeof g_ppg_policy_error); return rc; }
+    if ((rc = ppg_pipe_debug_check(prey)) != PPG_OK) return ppg_policy_mirror(prey, rc);
 #endif
 #ifdef PPG_DIRECT_PROFILE
-    if (dp_now) {
-        PPG_POL_TRY(prey, hipDeviceSynchronize());
-        std::vector<unsigned long long> host(dp_bytes / 8);
-        PPG_POL_TRY(prey, hipMemcpy(host.data(), dp_buf, dp_bytes, hipMemcpyDeviceToHost));
-        char name[512];
-        snprintf(name, sizeof name, "%s.fused", dp_path);
-        if (FILE *fo = fopen(name, "wb")) { fwrite(host.data(), 8, host.size(), fo); fclose(fo); }
-    }
+    if (g_ppg_direct_profile[2].armed && (rc = ppg_policy_dump_write(prey, g_ppg_direct_profile[2], ppg_direct_profile_bytes(prey), "fused")) != PPG_OK) return rc;
 #endif
     return PPG_OK;
 }
@@ -1960,19 +1911,15 @@ int ppg_policy_act(ppg_policy *pred, ppg_policy *prey, ppg_handle *const *handle
     if (!handles || !actions || n < 1 || n > ppgpol::MAX_HANDLES || !handles[0]) return ppg_policy_fail(any, PPG_EINVAL, "bad handle list");
     if (flags & ~(PPG_POLICY_SAMPLE | PPG_POLICY_SEED_ON_DEVICE)) return ppg_policy_fail(any, PPG_EINVAL, "unknown policy flags 0x%x", flags);
     for (int32_t k = 0; k < n; ++k)   // (the policy kernels read 64 predator rows per env)
-        if (handles[k] && handles[k]->base.cap_pred != 64) {
-            const int rc = ppg_policy_fail(any, PPG_EINVAL, "handle %d has %d predator rows; the policy kernels take handles with 64", k,
-                                           handles[k]->base.cap_pred);
-            memcpy(g_ppg_policy_error, any->err, sizeof g_ppg_policy_error);   // (ppg_policy_last_error(NULL))
-            return rc;
-        }
+        if (handles[k] && handles[k]->base.cap_pred != 64)
+            return ppg_policy_mirror(any, ppg_policy_fail(any, PPG_EINVAL, "handle %d has %d predator rows; the policy kernels take handles with 64", k,
+                                                          handles[k]->base.cap_pred));
     if (pred && prey && pred->pipe && prey->pipe && pred->device == prey->device && pred->grid == prey->grid && ppg_fused_enabled()) {
         const int rc = ppg_policy_run_fused(pred, prey, handles, n, actions, flags, seed, logits_pred, logits_prey, stream);
         if (rc != 1) return rc;
     }
     if (flags & PPG_POLICY_SEED_ON_DEVICE)
         return ppg_policy_fail(any, PPG_EINVAL, "PPG_POLICY_SEED_ON_DEVICE is for the one-launch form: both species' pipeline policies on one device");
-    // (a failure is also reported through ppg_policy_last_error(NULL), whichever of the two policies it came from)
     // The predators are few (a third of the chip's workgroup slots at 4096 envs): their launch goes to a side stream that is
     // forked from and joined back into `stream` with events, so that it fills the CUs the prey launch leaves idle.
     void *pred_stream = stream;
@@ -1992,11 +1939,11 @@ int ppg_policy_act(ppg_policy *pred, ppg_policy *prey, ppg_handle *const *handle
     const bool one_plan = pred && prey && !side;   // (same stream: the prey call's plan launch computes the predators' plan too)
     if (prey) {
         const int rc = ppg_policy_run(prey, 1, handles, n, actions, flags, seed, logits_prey, stream, one_plan ? pred : nullptr);
-        if (rc != PPG_OK) { memcpy(g_ppg_policy_error, prey->err, sizeof g_ppg_policy_error); return rc; }
+        if (rc != PPG_OK) return ppg_policy_mirror(prey, rc);
     }
     if (pred) {
         const int rc = ppg_policy_run(pred, 0, handles, n, actions, flags, seed, logits_pred, pred_stream, nullptr, one_plan);
-        if (rc != PPG_OK) { memcpy(g_ppg_policy_error, pred->err, sizeof g_ppg_policy_error); return rc; }
+        if (rc != PPG_OK) return ppg_policy_mirror(pred, rc);
     }
     if (side) {
         PPG_POL_TRY(pred, hipEventRecord(pred->join, pred->side));
