@@ -526,6 +526,59 @@ typedef struct ppg_record_buffers {
 int ppg_record(ppg_handle *h, const ppg_record_buffers *buf, uint64_t step, uint32_t flags, int16_t *prev_row, int16_t *next_row,
                void *stream);
 
+/* ---- observations and actions into a compact per-species sample store ------------------------------------------------
+ * ppg_record_obs appends the observation rows IN USE of the handle's last call -- exactly ppg_record's in_use: the first
+ * n_pred_rows / n_prey_rows rows of each species' region, each count taken as min(max(n, 0), capacity of the region) -- as step t to
+ * two caller-owned dense stores, one per species (s = 0 predators, 1 prey), and writes down which (t, b, r) every slot holds.  The slot
+ * number is then a learner's sample index: obs[s][k] is dense, returns / advantages / values are one index_select by sample[s][k].
+ * Two launches (one wavefront, then one wavefront per env; csrc/ppg_obs_store.h), no atomics.  All tensors of ppg_obs_store are
+ * contiguous device memory; B, S and the observation geometry are the handle's.
+ *   Order    envs in ascending b, within an env the rows in use in ascending r.  With c_s = cursor[s] before the call (taken as
+ *            min(max(c_s, 0), capacity[s])) and off_s[b] = the rows of species s in use in the envs < b, row r of env b gets slot
+ *            k = c_s + off_s[b] + r (prey: r - pred_capacity in place of r).
+ *   Stores   if k < capacity[s]:  obs[s][k]    = the row's blk_s elements, byte for byte (PPG_OBS_F32 on a float64 handle: every element
+ *                                                rounded to float32, to nearest even)
+ *                                 sample[s][k] = (t * B + b) * S + r
+ *                                 action[s][k] = PPG_ACTION_UNSET          (if action[] is given)
+ *                                 slot[t][b][r] = k
+ *   Overflow if k >= capacity[s] the row is dropped whole: slot[t][b][r] = -1 and no element of the store is written for it.  After
+ *            the call cursor[s] = min(c_s + total_s, capacity[s]) and cursor[2 + s] has grown by the number of rows dropped.  A
+ *            capacity of 0 drops every row.  No value read from device memory (cursor, the per-env bases, slot[t-1]) becomes an
+ *            address before it was compared with capacity[s].
+ *   Rows not in use get slot[t][b][r] = -1: all B * S entries of slot[t] are written, and no other element of slot is.
+ *   Actions  (actions != NULL, action[] given, t > 0)  `actions` is the [B,S] int8 tensor the handle's last step was given: it is
+ *            indexed by the rows of the PREVIOUS output, whose observations it answers.  For every (b, r) with
+ *            k = slot[t-1][b][r] and 0 <= k < capacity[s] (k is read from memory: it is range-checked, a word outside is ignored)
+ *            the call writes action[s][k] = actions[b][r].  So action[s][k] is the action taken FROM the observation in slot k,
+ *            written one call later; the slots of the last recorded step keep PPG_ACTION_UNSET.  An env whose call t was an
+ *            auto-reset gets the bytes stored all the same: the step ignored them, and its rows of step t - 1 are terminal.  With
+ *            device-drawn random actions (PPG_STEP_RANDOM_ACTIONS) there is no tensor to pass: actions = NULL.
+ *   Step     flags without PPG_OBS_STEP_ON_DEVICE: t = step; a step outside [0, horizon) is PPG_EINVAL.  With it `step` is the
+ *            address of an int32 in DEVICE memory that both kernels read when they run (as PPG_RECORD_STEP_ON_DEVICE; pass the same
+ *            word to ppg_record and count it up behind both); if the word is outside [0, horizon) NOTHING is written, the cursor
+ *            included: a replay past the horizon stores nothing.
+ * PPG_EINVAL (text in ppg_last_error, nothing is launched): st NULL; slot, cursor, sample[s] or obs[s] NULL; horizon < 1; a
+ * capacity < 0 or above INT32_MAX (slot holds int32); horizon * B * S above INT32_MAX (sample holds int32); only one of the two
+ * action[] pointers set; PPG_OBS_F32 on a handle whose observations are narrower than float32 (bfloat16); a host step outside
+ * [0, horizon); a NULL device address; unknown flag bits.
+ * The call does not touch the link snapshot and no env state, and may stand before or behind the ppg_record of the same step.  The
+ * per-env slot bases live in a library-owned [B,2] int64 scratch (allocated by the first call, freed by ppg_destroy).  Asynchronous
+ * on `stream`, ordered behind the handle's last step on that stream. */
+#define PPG_ACTION_UNSET (-128)          /* action[k] of a slot whose action has not been recorded (yet) */
+typedef struct ppg_obs_store {
+    int32_t  horizon;        /* T */
+    void    *obs[2];         /* [capacity[s], blk_s] elements; s = 0 predators, 1 prey; blk_s = the elements of one observation
+                                row of the handle (channels * R_s * R_s, the handle's own geometry: base, gen-2, walls, drive) */
+    int64_t  capacity[2];    /* rows each store can hold */
+    int32_t *sample[2];      /* [capacity[s]]  (t * B + b) * S + r of the row held in slot k */
+    int8_t  *action[2];      /* [capacity[s]]  may both be NULL */
+    int32_t *slot;           /* [T,B,S]  slot of row r of step t in its species' store, or -1 */
+    int64_t *cursor;         /* device int64 [4]: rows stored {pred, prey}, rows dropped {pred, prey} */
+} ppg_obs_store;
+#define PPG_OBS_STEP_ON_DEVICE 0x1u   /* as PPG_RECORD_STEP_ON_DEVICE */
+#define PPG_OBS_F32            0x2u   /* float64 observations are stored as float32 (as PPG_PACK_F32); other dtypes copied */
+int ppg_record_obs(ppg_handle *h, const ppg_obs_store *st, uint64_t step, uint32_t flags, const int8_t *actions, void *stream);
+
 /* ---- returns and advantages over a recorded horizon ------------------------------------------------------------------
  * What a learner does with the maps of ppg_link: the backward recursions over n_steps recorded calls, discounted returns G and
  * generalised advantages A, in ONE launch (one wavefront per env, the values of step t + 1 in LDS; csrc/ppg_backward.h).  All

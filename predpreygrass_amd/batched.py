@@ -469,20 +469,66 @@ class BatchedPredPreyGrass:
         link() and writes no buffer.  Returns link()'s (prev_row, next_row): the env's own tensors, written exactly as by link().
         stream (optional): as in link()."""
         shape = self._trajectory_args(reward=reward, in_use=in_use, terminated=terminated, truncated=truncated, next_row=next_row)
-        if isinstance(t, torch.Tensor):
-            if t.dtype != torch.int32 or t.numel() != 1 or t.device != self.device:
-                raise ValueError(f"t must be an int or a one-element int32 tensor on {self.device}")
-            step, flags = t.data_ptr(), _abi.RECORD_STEP_ON_DEVICE
-        else:
-            step, flags = int(t), 0
-            if not 0 <= step < shape[0]:
-                raise ValueError(f"t = {step} is outside [0, {shape[0]})")
+        step, on_device = self._step_index(t, shape[0])
+        flags = _abi.RECORD_STEP_ON_DEVICE if on_device else 0
         buf = _abi.PpgRecordBuffers(shape[0], reward.data_ptr(), in_use.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
                                     next_row.data_ptr())
         prev_row, link_next = self._link_tensors(stream)
         self._check(self._lib.ppg_record(self._handle, C.byref(buf), step, flags, C.c_void_p(prev_row.data_ptr()),
                                          C.c_void_p(link_next.data_ptr()), self._stream(stream)), "ppg_record")
         return prev_row, link_next
+
+    def _step_index(self, t, T):
+        """The step argument of record() / record_obs(): (value or device address, whether the kernel reads it on the device)."""
+        if isinstance(t, torch.Tensor):
+            if t.dtype != torch.int32 or t.numel() != 1 or t.device != self.device:
+                raise ValueError(f"t must be an int or a one-element int32 tensor on {self.device}")
+            return t.data_ptr(), True
+        step = int(t)
+        if not 0 <= step < T:
+            raise ValueError(f"t = {step} is outside [0, {T})")
+        return step, False
+
+    def record_obs(self, store, t, actions=None, f32=False, stream=None):
+        """Append the observation rows in use of this call's output, as step t, to a compact per-species sample store
+        (`ppg_record_obs`, include/ppg.h: order, overflow and the elements written are stated there), in two launches.
+        store: a `trajectory.ObservationStore`, or any object with its tensors -- `horizon` T, `capacity` (n_pred, n_prey),
+        `obs` [2] of [rows >= capacity, C, R, R] in the env's observation dtype (float32 with f32=True on a float64 env), `sample` [2]
+        int32 [rows], `action` None or [2] int8 [rows], `slot` int32 [T,B,S], `cursor` int64 [4].
+        t: as in record().  actions: the int8 [B,S] tensor the env's last step was given (they answer the observations stored by the
+        previous record_obs()), or None -- no actions are stored (device-drawn random actions).
+        stream (optional): launch on this torch.cuda.Stream instead of torch's current stream."""
+        T, B, S = int(store.horizon), self.batch_size, self.S
+        if f32 and self.obs_dtype == torch.bfloat16:
+            raise ValueError("f32=True is for float64 (and float32) observations, not bfloat16")
+        dtype = torch.float32 if f32 and self.obs_dtype == torch.float64 else self.obs_dtype
+        cursor = self._tensor_arg("store.cursor", store.cursor, (torch.int64,), (4,))
+
+        def rows(name, x, dtypes, shape, capacity):
+            ptr = self._tensor_arg(name, x, dtypes, (None,) + shape)
+            if x.shape[0] < capacity:
+                raise ValueError(f"{name} has {x.shape[0]} rows, fewer than the capacity {capacity}")
+            return ptr.value or cursor.value   # (an empty tensor has no address: capacity 0, nothing is addressed through it)
+        st = _abi.PpgObsStore()
+        st.horizon = T
+        if actions is not None and store.action is None:
+            raise ValueError("actions were given but the store keeps none")
+        for s, src in enumerate((self.obs_pred, self.obs_prey)):
+            capacity = int(store.capacity[s])
+            if capacity < 0:
+                raise ValueError(f"store.capacity[{s}] = {capacity} < 0")
+            st.capacity[s] = capacity
+            st.obs[s] = rows(f"store.obs[{s}]", store.obs[s], (dtype,), tuple(src.shape[2:]), capacity)
+            st.sample[s] = rows(f"store.sample[{s}]", store.sample[s], (torch.int32,), (), capacity)
+            if store.action is not None:
+                st.action[s] = rows(f"store.action[{s}]", store.action[s], (torch.int8,), (), capacity)
+        st.slot = self._tensor_arg("store.slot", store.slot, (torch.int32,), (T, B, S)).value
+        st.cursor = cursor.value
+        step, on_device = self._step_index(t, T)
+        flags = (_abi.OBS_STEP_ON_DEVICE if on_device else 0) | (_abi.OBS_F32 if f32 else 0)
+        act = None if actions is None else self._tensor_arg("actions", actions, (torch.int8,), (B, S))
+        self._check(self._lib.ppg_record_obs(self._handle, C.byref(st), step, flags, act, self._stream(stream)), "ppg_record_obs")
+        return store
 
     def backward(self, reward, next_row, in_use, terminated, truncated, gamma, lam=1.0, values=None, returns=True,
                  advantages=None, stream=None):

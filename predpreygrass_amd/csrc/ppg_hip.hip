@@ -291,6 +291,24 @@ static int backend_record(ppg_handle *h, const ppg::RecordParams &K, void *strea
     return PPG_OK;
 }
 
+// ---- ppg_record_obs: the rows in use appended to a per-species sample store (ppg_obs_store.h) ------------------------
+extern "C" __global__ void __launch_bounds__(64) ppg_obs_scan(const ppg::ObsStoreParams K) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[ppg::OBS_SCAN_LDS_BYTES];
+    ppg::obs_scan_main(*PPG_KERNARG_PTR(ppg::ObsStoreParams, K), lds);
+}
+extern "C" __global__ void __launch_bounds__(64) ppg_obs_rows(const ppg::ObsStoreParams K) {
+    ppg::obs_rows_main(*PPG_KERNARG_PTR(ppg::ObsStoreParams, K));
+}
+
+static int backend_record_obs(ppg_handle *h, const ppg::ObsStoreParams &K, void *stream) {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(ppg_obs_scan, dim3(1), dim3(64), 0, (hipStream_t)stream, K);
+    hipLaunchKernelGGL(ppg_obs_rows, dim3((unsigned)K.batch), dim3(64), 0, (hipStream_t)stream, K);
+    PPG_HIP_TRY(h, hipGetLastError());
+    return PPG_OK;
+}
+
 // ---- ppg_backward: returns and GAE over a recorded horizon (ppg_backward.h) ---------------------------------------
 extern "C" __global__ void __launch_bounds__(64) ppg_backward_rows(const ppg::BackwardParams K) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[ppg::BACKWARD_LDS_BYTES];

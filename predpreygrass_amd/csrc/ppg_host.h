@@ -22,6 +22,7 @@
 #include "ppg_link.h"
 #include "ppg_record.h"
 #include "ppg_backward.h"
+#include "ppg_obs_store.h"
 
 // How a handle's step is scheduled (never what it computes): wavefronts per workgroup, the row count from which helper wavefronts
 // stay, and -- cooperative kernels -- how many envs share a workgroup (0 = one env per workgroup, the ppg[w]_step kernels).
@@ -54,6 +55,7 @@ struct ppg_handle {
     uint64_t fetch_hint;        // bytes the next ppg_fetch copies in its first (usually only) transfer
     int32_t *link_dev;          // library-owned snapshot of ppg_link: ids [B,S] | episode [B] | row counts [B,2] (NULL until first used)
     int32_t link_valid;         // the snapshot is one the next ppg_link may link to (0: first call, or a reset since)
+    int64_t *obs_base_dev;      // library-owned [B,2] slot bases of ppg_record_obs (NULL until first used)
     int32_t backward_prefetch;  // ppg_backward requests step t - 1's inputs before step t's gather (PPG_BACKWARD_PREFETCH, read at create)
     ppg_config cfg;
     ppg_config_gen2 cfg2;
@@ -564,6 +566,19 @@ static int backend_record(ppg_handle *, const ppg::RecordParams &K, void *) {
     return PPG_OK;
 }
 #endif
+// the two launches of ppg_record_obs (ppg_obs_store.h)
+#ifndef PPG_WAVE_EMU
+static int backend_record_obs(ppg_handle *h, const ppg::ObsStoreParams &K, void *stream);
+#else
+// (CPU test build: defined here for the same reason as backend_link)
+static void ppg_obs_scan_entry(void *arg) { ppg::obs_scan_main(*(const ppg::ObsStoreParams *)arg, wv::emu().lds); }
+static void ppg_obs_rows_entry(void *arg) { ppg::obs_rows_main(*(const ppg::ObsStoreParams *)arg); }
+static int backend_record_obs(ppg_handle *, const ppg::ObsStoreParams &K, void *) {
+    wv::run_block(ppg_obs_scan_entry, (void *)&K, 0, ppg::OBS_SCAN_LDS_BYTES, 1);
+    for (int b = 0; b < K.batch; ++b) wv::run_block(ppg_obs_rows_entry, (void *)&K, b, 16, 1);
+    return PPG_OK;
+}
+#endif
 // the launch of ppg_backward (ppg_backward.h)
 #ifndef PPG_WAVE_EMU
 static int backend_backward(ppg_handle *h, const ppg::BackwardParams &K, void *stream);
@@ -626,6 +641,7 @@ static int ppg_create_common(const ppg_config *cfg, const ppg_config_gen2 *cfg2,
     h->vis_dev = nullptr;
     h->fetch_dev = nullptr; h->fetch_cap = 0; h->fetch_hint = 0;
     h->link_dev = nullptr; h->link_valid = 0;
+    h->obs_base_dev = nullptr;
     h->drive = (cfg && (cfg->n_drive[0] > 0 || cfg->n_drive[1] > 0)) ? 1 : 0;
     int rc = cfg2 ? ppg_validate_and_layout_gen2(h) : ppg_validate_and_layout(h);
     if (rc == PPG_OK) ppg_coop_layout(h);
@@ -659,6 +675,8 @@ int ppg_destroy(ppg_handle *h) {
     if (!h) return PPG_OK;
     if (h->link_dev) backend_free(h, h->link_dev);
     h->link_dev = nullptr;
+    if (h->obs_base_dev) backend_free(h, h->obs_base_dev);
+    h->obs_base_dev = nullptr;
     if (h->resident_dev) backend_free(h, h->resident_dev);
     h->resident_dev = nullptr;
     backend_release(h);
@@ -1246,6 +1264,47 @@ int ppg_record(ppg_handle *h, const ppg_record_buffers *buf, uint64_t step, uint
     rc = backend_record(h, K, stream);
     if (rc == PPG_OK) h->link_valid = 1;
     return rc;
+}
+
+int ppg_record_obs(ppg_handle *h, const ppg_obs_store *st, uint64_t step, uint32_t flags, const int8_t *actions, void *stream) {
+    if (!h) return PPG_EINVAL;
+    if (!st) return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: st is NULL");
+    if (!st->slot || !st->cursor || !st->sample[0] || !st->sample[1] || !st->obs[0] || !st->obs[1])
+        return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: slot, cursor, a sample[] or an obs[] of ppg_obs_store is NULL");
+    if (st->horizon < 1) return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: horizon %d < 1", st->horizon);
+    for (int s = 0; s < 2; ++s)
+        if (st->capacity[s] < 0 || st->capacity[s] > INT32_MAX)
+            return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: capacity[%d] = %lld outside [0, 2^31)", s, (long long)st->capacity[s]);
+    if ((uint64_t)st->horizon * (uint64_t)h->batch * (uint64_t)h->base.S > (uint64_t)INT32_MAX)
+        return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: horizon %d x %d envs x %d rows does not fit the int32 sample index", st->horizon, h->batch, h->base.S);
+    if (!st->action[0] != !st->action[1]) return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: only one of the two action[] pointers is set");
+    if (flags & ~(PPG_OBS_STEP_ON_DEVICE | PPG_OBS_F32)) return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: unknown flag bits 0x%x", flags);
+    const bool on_device = (flags & PPG_OBS_STEP_ON_DEVICE) != 0;
+    if (on_device && !step) return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: PPG_OBS_STEP_ON_DEVICE with a NULL address");
+    if (!on_device && step >= (uint64_t)st->horizon)
+        return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: step %llu outside [0, %d)", (unsigned long long)step, st->horizon);
+    ppg::ObsStoreParams K;
+    memset(&K, 0, sizeof K);
+    ppg_pack_geometry(h, (flags & PPG_OBS_F32) ? PPG_PACK_F32 : 0u, K.blk[0], K.blk[1], K.src_elem, K.dst_elem);
+    if ((flags & PPG_OBS_F32) && K.src_elem < 4)
+        return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: PPG_OBS_F32 on a handle with %d-byte observation elements", K.src_elem);
+    if (!h->obs_base_dev) {
+        const int rc = backend_alloc(h, (void **)&h->obs_base_dev, (size_t)h->batch * 2 * sizeof(int64_t));
+        if (rc != PPG_OK) return rc;
+    }
+    K.batch = h->batch; K.S = h->base.S; K.cap_pred = h->base.cap_pred; K.cap_prey = h->base.cap_prey;
+    K.T = st->horizon; K.step_on_device = on_device;
+    K.step = on_device ? 0 : (int32_t)step;
+    K.step_dev = on_device ? (const int32_t *)(uintptr_t)step : nullptr;
+    K.env_state = h->bufs.env_state;
+    K.src[0] = (const unsigned char *)h->bufs.obs_pred; K.src[1] = (const unsigned char *)h->bufs.obs_prey;
+    for (int s = 0; s < 2; ++s) {
+        K.dst[s] = (unsigned char *)st->obs[s]; K.capacity[s] = st->capacity[s];
+        K.sample[s] = st->sample[s]; K.action[s] = st->action[s];
+    }
+    K.slot = st->slot; K.cursor = st->cursor; K.base = h->obs_base_dev;
+    K.actions = st->action[0] ? actions : nullptr;
+    return backend_record_obs(h, K, stream);
 }
 
 int ppg_backward(ppg_handle *h, int32_t n_steps, const double *reward, const int16_t *next_row, const uint8_t *in_use,

@@ -39,6 +39,22 @@ With `step_on_device` the kernel reads the step index when it runs and an increm
 the launch depends on a host value and a recorded step can be replayed; `len(traj)` and the backward methods read the index back
 once.  A record past the horizon then stores nothing (it still links) instead of raising.  Not for `SubBatchedPredPreyGrass` as a
 whole: give each sub-batch its own AgentTrajectories.
+
+What the agents saw and did is stored next to that on request, compacted: `obs_rows=(n_pred, n_prey)` gives the trajectory an
+`ObservationStore`, and `record(actions)` then also appends the observation rows in use -- about a fifth of the [B,capacity] rows at
+the default population -- to one dense tensor per species (`env.record_obs()`, `ppg_record_obs`, csrc/ppg_obs_store.h: two launches,
+nothing read back, so it replays inside GraphedCollector's graph).  The slot a row lands in is the learner's sample index:
+
+    traj = AgentTrajectories(env, horizon=T, obs_rows=(T * B * 12, T * B * 40))
+    for t in range(T):
+        env.step(actions); traj.record(actions)        # `actions` answered the observations stored one record() earlier
+    G, A = traj.returns_and_gae(values, 0.99, 0.95)
+    n, obs, index, action = traj.samples(PREY)         # dense [n,C,R,R], int64 [n] flat (t,b,r), int8 [n]; one read-back
+    g, a = traj.flat(G, PREY), traj.flat(A, PREY)      # [n]: G.reshape(-1)[index]
+
+`action[k]` is the action taken FROM the observation in slot k; it is written by the record() one step later, so the samples of the
+last recorded step (and of rows whose env was not stepped again) hold `_abi.ACTION_UNSET`.  Rows that no longer fit the store are
+dropped whole and counted (`store.counts()`).
 """
 from __future__ import annotations
 
@@ -47,8 +63,80 @@ import torch
 from . import _abi
 
 
+class ObservationStore:
+    """The tensors of `ppg_obs_store` (include/ppg.h) for one env: per species s (0 predators, 1 prey) `obs[s]` [rows[s],C,R,R],
+    `sample[s]` int32 [rows[s]] -- the flat index (t * B + b) * S + r of the row in slot k -- and `action[s]` int8 [rows[s]] (None
+    with actions=False); `slot` int32 [T,B,S], the slot of every row of every step or -1; `cursor` int64 [4] on the device: rows stored
+    {pred, prey}, rows dropped {pred, prey}.  dtype: the env's observation dtype (default), or torch.float32 on a float64 env -- the
+    rows are then rounded to float32 as they are stored."""
+
+    def __init__(self, env, horizon, rows, dtype=None, actions=True):
+        self.env, self.horizon = env, int(horizon)
+        self.capacity = (int(rows[0]), int(rows[1]))
+        if self.horizon < 1 or min(self.capacity) < 0:
+            raise ValueError("horizon must be >= 1 and rows >= 0")
+        dtype = env.obs_dtype if dtype is None else dtype
+        if dtype != env.obs_dtype and not (dtype == torch.float32 and env.obs_dtype == torch.float64):
+            raise ValueError(f"dtype must be the env's {env.obs_dtype} (or torch.float32 on a float64 env), not {dtype}")
+        self.f32 = dtype != env.obs_dtype
+        dev = env.device
+        self.obs = [torch.zeros((n,) + tuple(src.shape[2:]), dtype=dtype, device=dev)
+                    for n, src in zip(self.capacity, (env.obs_pred, env.obs_prey))]
+        self.sample = [torch.zeros((n,), dtype=torch.int32, device=dev) for n in self.capacity]
+        self.action = [torch.full((n,), _abi.ACTION_UNSET, dtype=torch.int8, device=dev) for n in self.capacity] if actions else None
+        self.slot = torch.full((self.horizon, env.batch_size, env.S), -1, dtype=torch.int32, device=dev)
+        self.cursor = torch.zeros((4,), dtype=torch.int64, device=dev)
+
+    def clear(self):
+        """Start filling from slot 0 again (the tensors keep their bytes: everything below the cursor is rewritten as it moves)."""
+        self.cursor.zero_()
+        return self
+
+    def counts(self):
+        """((stored, dropped) of the predators, (stored, dropped) of the prey): one read-back."""
+        c = self.cursor.tolist()
+        return (c[0], c[2]), (c[1], c[3])
+
+    def record(self, t, actions=None, stream=None):
+        """env.record_obs() into this store."""
+        self.env.record_obs(self, t, actions if self.action is not None else None, f32=self.f32, stream=stream)
+        return self
+
+    def record_obs_torch(self, t, actions=None):
+        """record(t, actions) as torch ops: the same bytes, `nonzero`-based, so the host waits for the device at every call (timing
+        baseline, fallback).  t: an int."""
+        env, t = self.env, int(t)
+        if not 0 <= t < self.horizon:
+            raise ValueError(f"t = {t} is outside [0, {self.horizon})")
+        B, S, dev = env.batch_size, env.S, env.device
+        cursor = self.cursor.tolist()
+        slot_t = torch.full((B, S), -1, dtype=torch.int32, device=dev)
+        for s, (first, cap, src, word) in enumerate(((0, env.pred_capacity, env.obs_pred, _abi.ENV_N_PRED_ROWS),
+                                                     (env.pred_capacity, env.prey_capacity, env.obs_prey, _abi.ENV_N_PREY_ROWS))):
+            n = env.env_state[:, word:word + 1].clamp(0, cap)
+            b, j = (torch.arange(cap, device=dev).unsqueeze(0) < n).nonzero(as_tuple=True)   # env-major, rows ascending
+            k = cursor[s] + torch.arange(b.numel(), device=dev)
+            keep = k < self.capacity[s]
+            b, j, k = b[keep], j[keep], k[keep]
+            self.obs[s][k] = src[b, j].to(self.obs[s].dtype)
+            self.sample[s][k] = ((t * B + b) * S + first + j).to(torch.int32)
+            if self.action is not None:
+                self.action[s][k] = _abi.ACTION_UNSET
+            slot_t[b, first + j] = k.to(torch.int32)
+            if actions is not None and self.action is not None and t > 0:
+                prev = self.slot[t - 1][:, first:first + cap]
+                ok = (prev >= 0) & (prev < self.capacity[s])
+                self.action[s][prev[ok].long()] = actions[:, first:first + cap][ok]
+            end = cursor[s] + int(keep.numel())
+            cursor[2 + s] += end - min(end, self.capacity[s])
+            cursor[s] = min(end, self.capacity[s])
+        self.slot[t].copy_(slot_t)
+        self.cursor.copy_(torch.tensor(cursor, dtype=torch.int64))
+        return self
+
+
 class AgentTrajectories:
-    def __init__(self, env, horizon, step_on_device=False):
+    def __init__(self, env, horizon, step_on_device=False, obs_rows=None):
         self.env = env
         self.horizon = int(horizon)
         if self.horizon < 1:
@@ -66,6 +154,9 @@ class AgentTrajectories:
         self.step_on_device = bool(step_on_device)
         self.t_dev = torch.zeros((1,), dtype=torch.int32, device=dev) if self.step_on_device else None
         self._t = 0
+        # obs_rows = (n_pred, n_prey): record() also appends the observation rows in use (and the actions it is given) to a compact
+        # store of that many rows per species -- `store`, read through samples() and flat()
+        self.store = ObservationStore(env, self.horizon, obs_rows) if obs_rows is not None else None
 
     @property
     def t(self):
@@ -87,26 +178,61 @@ class AgentTrajectories:
             self.t_dev.zero_()
         else:
             self._t = 0
+        if self.store is not None:
+            self.store.clear()
         return self
 
     def __len__(self):
         return self.t
 
-    def record(self):
+    def record(self, actions=None):
         """Store the output of the env's last call as step t.  Call it after every env.step of the trajectory, on the stream the
         step ran on (torch's current stream).  ONE launch: `env.record()` (`ppg_record`: the link kernel plus the stores;
         record_torch() is the same as torch ops).  With step_on_device the launch reads t_dev and an increment of it follows on the
-        same stream; past the horizon such a call stores nothing."""
+        same stream; past the horizon such a call stores nothing.
+        With a store (obs_rows) two more launches follow with the same step index: `env.record_obs()` appends the observation rows in
+        use; actions: the int8 [B,S] tensor the step was given, stored as the actions of the previous record()'s samples (None: the
+        actions stay ACTION_UNSET, e.g. device-drawn random actions)."""
         env = self.env
         if self.step_on_device:
             env.record(self.reward, self.in_use, self.terminated, self.truncated, self.next_row, self.t_dev)
+            if self.store is not None:
+                self.store.record(self.t_dev, actions)
             self.t_dev.add_(1)
             return self
         if self._t >= self.horizon:
             raise RuntimeError(f"the trajectory is full ({self.horizon} steps): clear() it")
         env.record(self.reward, self.in_use, self.terminated, self.truncated, self.next_row, self._t)
+        if self.store is not None:
+            self.store.record(self._t, actions)
         self._t += 1
         return self
+
+    def record_obs_torch(self, actions=None):
+        """record(actions) of a trajectory with a store as torch ops: record_torch() plus ObservationStore.record_obs_torch() -- the
+        same bytes; the host waits for the device (timing baseline, fallback)."""
+        if self.store is None:
+            raise RuntimeError("record_obs_torch() needs a store: AgentTrajectories(..., obs_rows=(n_pred, n_prey))")
+        t = self.t
+        self.record_torch()
+        self.store.record_obs_torch(t, actions)
+        return self
+
+    def samples(self, species):
+        """(n, obs[:n], index[:n], action[:n]) of one species (0 predators, 1 prey): the rows stored so far (one read-back), their
+        observations [n,C,R,R], the flat index (t * B + b) * S + r of each as int64 -- `x.reshape(-1)[index]` picks a sample's element
+        of any [len,B,S] tensor, which is what flat() does -- and the actions taken from them (None for a store without actions).
+        Samples are ordered by step, then env, then row."""
+        if self.store is None:
+            raise RuntimeError("samples() needs a store: AgentTrajectories(..., obs_rows=(n_pred, n_prey))")
+        st = self.store
+        n = int(st.cursor[species].item())
+        return n, st.obs[species][:n], st.sample[species][:n].long(), None if st.action is None else st.action[species][:n]
+
+    def flat(self, x, species):
+        """The elements of a [len,B,S] tensor (returns, advantages, values ...) that belong to the stored samples of a species, in
+        sample order: x.reshape(-1)[index[:n]]."""
+        return x.reshape(-1)[self.samples(species)[2]]
 
     def record_torch(self):
         """record() as torch ops behind `env.link()`: the same bytes, about nineteen small launches (timing baseline, fallback)."""
@@ -238,9 +364,10 @@ class GraphedCollector:
             if act is not None:
                 act()
                 env.step(env.actions, auto_reset=auto_reset)
+                traj.record(env.actions)   # (a trajectory with a store keeps them as the actions of the previous step's samples)
             else:
                 env.step(random_actions=True, auto_reset=auto_reset)
-            traj.record()
+                traj.record()
         # (one uncaptured pass on a side stream first: lazy allocations of the library and of the env must not fall into the capture)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
