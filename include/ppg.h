@@ -579,6 +579,57 @@ typedef struct ppg_obs_store {
 #define PPG_OBS_F32            0x2u   /* float64 observations are stored as float32 (as PPG_PACK_F32); other dtypes copied */
 int ppg_record_obs(ppg_handle *h, const ppg_obs_store *st, uint64_t step, uint32_t flags, const int8_t *actions, void *stream);
 
+/* ---- the behaviour policy's log-probabilities into the sample store ---------------------------------------------------
+ * ppg_record_logp writes, for every sample that ppg_record_obs stored as step t, what the policy that acted on it thought: the
+ * log-probability of the action taken (PPO's ratio), the entropy, and on request the logits themselves (the distribution inputs of a
+ * KL term).  The logits are the float32 tensors ppg_policy_act wrote for the handle's CURRENT output -- logits_pred / logits_prey,
+ * [B * rows_s, n_actions[s]], env-major in row order: with off_s[b] = the rows of species s in use in the envs < b, row j of species s
+ * in env b is logits row i = off_s[b] + j.  They cannot be recomputed later from the stored observations: the kernels of
+ * ppg_policy_act round to bf16 between layers, and the actions were drawn from THESE numbers.  Either logits pointer may be NULL: that
+ * species is skipped (like a NULL policy in ppg_policy_act) and none of its tensors is touched.  `actions` is the [B,S] int8 tensor
+ * ppg_policy_act filled (required).  Two launches (one wavefront, then one wavefront per env and one lane per row;
+ * csrc/ppg_logp.h), no atomics, nothing read back.  All tensors are contiguous device memory; B, S and the row counts are the handle's.
+ *   Rows     species s, row j < n_s(b) -- the rows in use exactly as ppg_record_obs takes them: min(max(n, 0), rows of the region) --
+ *            with r = j (prey: pred_capacity + j), a = actions[b][r], k = st->slot[t][b][r], A = n_actions[s].
+ *   Stores   if 0 <= k < st->capacity[s] (k is read from memory: it is range-checked before it becomes an address):
+ *              logp[s][k]        = log-softmax of logits row i at a; quiet NaN if a is outside [0, A) (PPG_ACTION_UNSET, -1 ...): a
+ *                                  is compared with [0, A) and never used as an index
+ *              entropy[s][k]     = - sum p log p of the row               (if entropy[] is given)
+ *              dist[s][k][0..A)  = the row's A logits, bit for bit          (if dist[] is given)
+ *            Rows not in use, rows the store dropped (slot -1) and slot words outside the capacity write nothing, and no other
+ *            element of any tensor is written; st->obs, sample, action, slot and cursor are not written at all (cursor, obs, sample
+ *            and action are not even read and may be NULL).
+ *   Numbers  the float32 logits l are widened to float64; m = max l, e_a = exp(l_a - m), s = sum e_a in ascending a,
+ *            logp = (l_a - m) - log(s), entropy = log(s) - (sum e_a (l_a - m)) / s, each rounded ONCE to float32 at the store; no fused
+ *            multiply-add.  A logit of -inf is a masked action: legal while one logit of the row is finite, it contributes exactly 0 to
+ *            both sums (the term is skipped, never formed as 0 * inf) and its own logp is -inf.  A row without a finite maximum (all
+ *            -inf, a +inf) and a row that holds a NaN give NaN in logp and entropy; dist is copied all the same.
+ *   Step     t is the recorded step whose observations the logits were computed from: the handle's current output, which ppg_record /
+ *            ppg_record_obs stored as step t.  The call stands BEHIND ppg_policy_act and IN FRONT of the next ppg_step (the env state
+ *            words must still be those ppg_record_obs saw).  flags without PPG_LOGP_STEP_ON_DEVICE: t = step; a step outside
+ *            [0, horizon) is PPG_EINVAL.  With it `step` is the address of the int32 in DEVICE memory that ppg_record /
+ *            ppg_record_obs take and that is counted up behind them: it already names the NEXT step, so t = word - 1, read by both
+ *            kernels when they run; if t is outside [0, horizon) -- nothing recorded yet, or a replay past the horizon -- NOTHING is
+ *            written (t becomes an index only after that check).
+ * PPG_EINVAL (text in ppg_last_error, nothing is launched): st, out or actions NULL; st->slot NULL; logp[s] NULL for a species whose
+ * logits are given; only one of entropy[0] / entropy[1] or of dist[0] / dist[1] set; n_actions[s] outside 1..32 for a species whose
+ * logits are given; horizon < 1, a capacity < 0 or above INT32_MAX, horizon * B * S above INT32_MAX (what ppg_record_obs refuses); a
+ * host step outside [0, horizon); a NULL device address; unknown flag bits.  With both logits NULL the call checks its arguments and
+ * launches nothing.
+ * One handle per call: sub-batches that share one ppg_policy_act call share its logits tensor, which this call cannot split -- give
+ * each sub-batch its own act call.  The call touches no env state and not the link snapshot.  The per-env row offsets live in a
+ * library-owned [B,2] int32 scratch (allocated by the first call, freed by ppg_destroy).  Asynchronous on `stream`, ordered behind
+ * the ppg_policy_act that wrote the logits on that stream. */
+typedef struct ppg_logp_store {
+    float  *logp[2];      /* [capacity[s]]; required for a species whose logits are given */
+    float  *entropy[2];   /* [capacity[s]]; both NULL or both set */
+    float  *dist[2];      /* [capacity[s], n_actions[s]]; both NULL or both set */
+    int32_t n_actions[2]; /* 1..32 */
+} ppg_logp_store;
+#define PPG_LOGP_STEP_ON_DEVICE 0x1u
+int ppg_record_logp(ppg_handle *h, const ppg_obs_store *st, const ppg_logp_store *out, uint64_t step, uint32_t flags,
+                    const float *logits_pred, const float *logits_prey, const int8_t *actions, void *stream);
+
 /* ---- returns and advantages over a recorded horizon ------------------------------------------------------------------
  * What a learner does with the maps of ppg_link: the backward recursions over n_steps recorded calls, discounted returns G and
  * generalised advantages A, in ONE launch (one wavefront per env, the values of step t + 1 in LDS; csrc/ppg_backward.h).  All

@@ -22,6 +22,8 @@ RECORD_STEP_ON_DEVICE = 0x1
 # flags of ppg_record_obs, and what action[k] holds until the action of slot k is recorded
 OBS_STEP_ON_DEVICE, OBS_F32 = 0x1, 0x2
 ACTION_UNSET = -128
+# flags of ppg_record_logp
+LOGP_STEP_ON_DEVICE = 0x1
 # env_state words
 ENV_WORDS = 20
 (ENV_N_PRED_ROWS, ENV_N_PREY_ROWS, ENV_N_PRED_NEW, ENV_N_PREY_NEW, ENV_NEXT_PRED_ID, ENV_NEXT_PREY_ID,
@@ -144,6 +146,11 @@ class PpgObsStore(C.Structure):
                 ("action", C.c_void_p * 2), ("slot", C.c_void_p), ("cursor", C.c_void_p)]
 
 
+class PpgLogpStore(C.Structure):
+    """include/ppg.h: struct ppg_logp_store (the behaviour-policy tensors of trajectory.ObservationStore)."""
+    _fields_ = [("logp", C.c_void_p * 2), ("entropy", C.c_void_p * 2), ("dist", C.c_void_p * 2), ("n_actions", C.c_int32 * 2)]
+
+
 class PpgInitState(C.Structure):
     """include/ppg.h: struct ppg_init_state (host uint16 arrays, cells as (x << 8) | y)."""
     _fields_ = [("pred_xy", C.c_void_p), ("prey_xy", C.c_void_p), ("grass_xy", C.c_void_p), ("episode", C.c_uint32), ("reserved_", C.c_uint32)]
@@ -180,7 +187,7 @@ EXPORTED_SYMBOLS = [
     "ppg_rollout", "ppg_step_ordered", "ppg_create_gen2", "ppg_step_uniforms", "ppg_set_envs_in_flight", "ppg_set_wave_plan",
     "ppg_get_wave_plan", "ppg_rebalance", "ppg_set_resident_envs", "ppg_get_resident_envs",
     "ppg_export_grid", "ppg_walls_changed", "ppg_state_bytes", "ppg_export_state", "ppg_import_state", "ppg_pack_bytes", "ppg_pack",
-    "ppg_fetch_bytes", "ppg_fetch", "ppg_link", "ppg_record", "ppg_record_obs", "ppg_backward",
+    "ppg_fetch_bytes", "ppg_fetch", "ppg_link", "ppg_record", "ppg_record_obs", "ppg_record_logp", "ppg_backward",
     "ppg_lexkey", "ppg_lds_bytes", "ppg_step_kernel_name", "ppg_last_error",
 ] + POLICY_SYMBOLS + SPREAD_SYMBOLS
 
@@ -249,6 +256,9 @@ def bind(lib: C.CDLL) -> C.CDLL:
     lib.ppg_record.argtypes = [C.c_void_p, C.POINTER(PpgRecordBuffers), C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ppg_record_obs.restype = C.c_int
     lib.ppg_record_obs.argtypes = [C.c_void_p, C.POINTER(PpgObsStore), C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.ppg_record_logp.restype = C.c_int
+    lib.ppg_record_logp.argtypes = [C.c_void_p, C.POINTER(PpgObsStore), C.POINTER(PpgLogpStore), C.c_uint64, C.c_uint32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]   # logits_pred, logits_prey, actions, stream
     lib.ppg_backward.restype = C.c_int
     lib.ppg_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,   # handle, n_steps, five inputs
                                  C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]   # values, dtype, gamma, lam, G, A, stream

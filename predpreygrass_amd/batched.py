@@ -530,6 +530,54 @@ class BatchedPredPreyGrass:
         self._check(self._lib.ppg_record_obs(self._handle, C.byref(st), step, flags, act, self._stream(stream)), "ppg_record_obs")
         return store
 
+    def record_logp(self, store, t, logits, actions=None, stream=None):
+        """What the behaviour policy thought of the samples that record_obs() stored as step t: `store.logp[s][k]` = log pi(a|o) of the
+        action taken from slot k, `store.entropy[s][k]`, `store.dist[s][k]` = the logits (`ppg_record_logp`, include/ppg.h: the
+        arithmetic and the elements written are stated there), in two launches, nothing read back.  Call it behind
+        `FusedPolicy.act(..., logits=...)` and in front of the next step().
+        store: a `trajectory.ObservationStore(..., logp=(A_pred, A_prey))`, or any object with `horizon` T, `capacity`, `slot` int32
+        [T,B,S], `n_actions` (A_pred, A_prey), `logp` [2] float32 [rows >= capacity], `entropy` None or [2] likewise, `dist` None or [2]
+        float32 [rows, A_s].
+        t: the recorded step the env's current output was stored as -- an int in [0, T); or the one-element int32 tensor record()
+        takes, which already names the NEXT step: the kernels then use its value minus one and write nothing if that is outside [0, T).
+        logits: (logits_pred, logits_prey), float32 [B * capacity_s, A_s] as `FusedPolicy.act()` fills them; either may be None -- that
+        species is skipped.  actions: the int8 [B,S] tensor act() filled (default: `env.actions`).
+        stream (optional): launch on this torch.cuda.Stream instead of torch's current stream."""
+        T, B, S = int(store.horizon), self.batch_size, self.S
+        if getattr(store, "logp", None) is None:
+            raise ValueError("the store keeps no log-probabilities: ObservationStore(..., logp=(A_pred, A_prey))")
+        if len(logits) != 2:
+            raise ValueError("logits must be the pair (logits_pred, logits_prey); either may be None")
+        anchor = self._tensor_arg("store.slot", store.slot, (torch.int32,), (T, B, S))
+
+        def rows(name, x, shape, capacity):
+            ptr = self._tensor_arg(name, x, (torch.float32,), (None,) + shape)
+            if x.shape[0] < capacity:
+                raise ValueError(f"{name} has {x.shape[0]} rows, fewer than the capacity {capacity}")
+            return ptr.value or anchor.value   # (an empty tensor has no address: capacity 0, nothing is addressed through it)
+        st, out = _abi.PpgObsStore(), _abi.PpgLogpStore()
+        st.horizon, st.slot = T, anchor.value
+        lg = [None, None]
+        for s, cap in enumerate((self.pred_capacity, self.prey_capacity)):
+            capacity, A = int(store.capacity[s]), int(store.n_actions[s])
+            if capacity < 0:
+                raise ValueError(f"store.capacity[{s}] = {capacity} < 0")
+            if not 1 <= A <= 32:
+                raise ValueError(f"store.n_actions[{s}] = {A} is outside 1..32")
+            st.capacity[s], out.n_actions[s] = capacity, A
+            out.logp[s] = rows(f"store.logp[{s}]", store.logp[s], (), capacity)
+            if store.entropy is not None:
+                out.entropy[s] = rows(f"store.entropy[{s}]", store.entropy[s], (), capacity)
+            if store.dist is not None:
+                out.dist[s] = rows(f"store.dist[{s}]", store.dist[s], (A,), capacity)
+            if logits[s] is not None:
+                lg[s] = self._tensor_arg(f"logits[{s}]", logits[s], (torch.float32,), (B * cap, A))
+        step, on_device = self._step_index(t, T)
+        act = self._tensor_arg("actions", self.actions if actions is None else actions, (torch.int8,), (B, S))
+        self._check(self._lib.ppg_record_logp(self._handle, C.byref(st), C.byref(out), step, _abi.LOGP_STEP_ON_DEVICE if on_device else 0,
+                                              lg[0], lg[1], act, self._stream(stream)), "ppg_record_logp")
+        return store
+
     def backward(self, reward, next_row, in_use, terminated, truncated, gamma, lam=1.0, values=None, returns=True,
                  advantages=None, stream=None):
         """Discounted returns and generalised advantages over a recorded horizon in ONE launch (`ppg_backward`, include/ppg.h:

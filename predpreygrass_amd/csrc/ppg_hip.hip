@@ -309,6 +309,24 @@ static int backend_record_obs(ppg_handle *h, const ppg::ObsStoreParams &K, void 
     return PPG_OK;
 }
 
+// ---- ppg_record_logp: the behaviour policy's log-probabilities into the sample store (ppg_logp.h) --------------------
+extern "C" __global__ void __launch_bounds__(64) ppg_logp_scan(const ppg::LogpParams K) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[ppg::LOGP_SCAN_LDS_BYTES];
+    ppg::logp_scan_main(*PPG_KERNARG_PTR(ppg::LogpParams, K), lds);
+}
+extern "C" __global__ void __launch_bounds__(64) ppg_logp_rows(const ppg::LogpParams K) {
+    ppg::logp_rows_main(*PPG_KERNARG_PTR(ppg::LogpParams, K));
+}
+
+static int backend_record_logp(ppg_handle *h, const ppg::LogpParams &K, void *stream) {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(ppg_logp_scan, dim3(1), dim3(64), 0, (hipStream_t)stream, K);
+    hipLaunchKernelGGL(ppg_logp_rows, dim3((unsigned)K.batch), dim3(64), 0, (hipStream_t)stream, K);
+    PPG_HIP_TRY(h, hipGetLastError());
+    return PPG_OK;
+}
+
 // ---- ppg_backward: returns and GAE over a recorded horizon (ppg_backward.h) ---------------------------------------
 extern "C" __global__ void __launch_bounds__(64) ppg_backward_rows(const ppg::BackwardParams K) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[ppg::BACKWARD_LDS_BYTES];

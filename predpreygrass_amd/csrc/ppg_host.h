@@ -23,6 +23,7 @@
 #include "ppg_record.h"
 #include "ppg_backward.h"
 #include "ppg_obs_store.h"
+#include "ppg_logp.h"
 
 // How a handle's step is scheduled (never what it computes): wavefronts per workgroup, the row count from which helper wavefronts
 // stay, and -- cooperative kernels -- how many envs share a workgroup (0 = one env per workgroup, the ppg[w]_step kernels).
@@ -56,6 +57,7 @@ struct ppg_handle {
     int32_t *link_dev;          // library-owned snapshot of ppg_link: ids [B,S] | episode [B] | row counts [B,2] (NULL until first used)
     int32_t link_valid;         // the snapshot is one the next ppg_link may link to (0: first call, or a reset since)
     int64_t *obs_base_dev;      // library-owned [B,2] slot bases of ppg_record_obs (NULL until first used)
+    int32_t *logp_off_dev;      // library-owned [B,2] logits row offsets of ppg_record_logp (NULL until first used)
     int32_t backward_prefetch;  // ppg_backward requests step t - 1's inputs before step t's gather (PPG_BACKWARD_PREFETCH, read at create)
     ppg_config cfg;
     ppg_config_gen2 cfg2;
@@ -579,6 +581,19 @@ static int backend_record_obs(ppg_handle *, const ppg::ObsStoreParams &K, void *
     return PPG_OK;
 }
 #endif
+// the two launches of ppg_record_logp (ppg_logp.h)
+#ifndef PPG_WAVE_EMU
+static int backend_record_logp(ppg_handle *h, const ppg::LogpParams &K, void *stream);
+#else
+// (CPU test build: defined here for the same reason as backend_link)
+static void ppg_logp_scan_entry(void *arg) { ppg::logp_scan_main(*(const ppg::LogpParams *)arg, wv::emu().lds); }
+static void ppg_logp_rows_entry(void *arg) { ppg::logp_rows_main(*(const ppg::LogpParams *)arg); }
+static int backend_record_logp(ppg_handle *, const ppg::LogpParams &K, void *) {
+    wv::run_block(ppg_logp_scan_entry, (void *)&K, 0, ppg::LOGP_SCAN_LDS_BYTES, 1);
+    for (int b = 0; b < K.batch; ++b) wv::run_block(ppg_logp_rows_entry, (void *)&K, b, 16, 1);
+    return PPG_OK;
+}
+#endif
 // the launch of ppg_backward (ppg_backward.h)
 #ifndef PPG_WAVE_EMU
 static int backend_backward(ppg_handle *h, const ppg::BackwardParams &K, void *stream);
@@ -642,6 +657,7 @@ static int ppg_create_common(const ppg_config *cfg, const ppg_config_gen2 *cfg2,
     h->fetch_dev = nullptr; h->fetch_cap = 0; h->fetch_hint = 0;
     h->link_dev = nullptr; h->link_valid = 0;
     h->obs_base_dev = nullptr;
+    h->logp_off_dev = nullptr;
     h->drive = (cfg && (cfg->n_drive[0] > 0 || cfg->n_drive[1] > 0)) ? 1 : 0;
     int rc = cfg2 ? ppg_validate_and_layout_gen2(h) : ppg_validate_and_layout(h);
     if (rc == PPG_OK) ppg_coop_layout(h);
@@ -677,6 +693,8 @@ int ppg_destroy(ppg_handle *h) {
     h->link_dev = nullptr;
     if (h->obs_base_dev) backend_free(h, h->obs_base_dev);
     h->obs_base_dev = nullptr;
+    if (h->logp_off_dev) backend_free(h, h->logp_off_dev);
+    h->logp_off_dev = nullptr;
     if (h->resident_dev) backend_free(h, h->resident_dev);
     h->resident_dev = nullptr;
     backend_release(h);
@@ -1305,6 +1323,51 @@ int ppg_record_obs(ppg_handle *h, const ppg_obs_store *st, uint64_t step, uint32
     K.slot = st->slot; K.cursor = st->cursor; K.base = h->obs_base_dev;
     K.actions = st->action[0] ? actions : nullptr;
     return backend_record_obs(h, K, stream);
+}
+
+int ppg_record_logp(ppg_handle *h, const ppg_obs_store *st, const ppg_logp_store *out, uint64_t step, uint32_t flags,
+                    const float *logits_pred, const float *logits_prey, const int8_t *actions, void *stream) {
+    if (!h) return PPG_EINVAL;
+    if (!st || !out || !actions) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: st, out or actions is NULL");
+    if (!st->slot) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: slot of ppg_obs_store is NULL");
+    if (st->horizon < 1) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: horizon %d < 1", st->horizon);
+    for (int s = 0; s < 2; ++s)
+        if (st->capacity[s] < 0 || st->capacity[s] > INT32_MAX)
+            return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: capacity[%d] = %lld outside [0, 2^31)", s, (long long)st->capacity[s]);
+    if ((uint64_t)st->horizon * (uint64_t)h->batch * (uint64_t)h->base.S > (uint64_t)INT32_MAX)
+        return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: horizon %d x %d envs x %d rows does not fit the int32 sample index", st->horizon, h->batch, h->base.S);
+    const float *logits[2] = {logits_pred, logits_prey};
+    for (int s = 0; s < 2; ++s) {
+        if (!logits[s]) continue;
+        if (!out->logp[s]) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: logp[%d] is NULL but the species' logits are given", s);
+        if (out->n_actions[s] < 1 || out->n_actions[s] > 32)
+            return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: n_actions[%d] = %d outside 1..32", s, out->n_actions[s]);
+    }
+    if (!out->entropy[0] != !out->entropy[1]) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: only one of the two entropy[] pointers is set");
+    if (!out->dist[0] != !out->dist[1]) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: only one of the two dist[] pointers is set");
+    if (flags & ~PPG_LOGP_STEP_ON_DEVICE) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: unknown flag bits 0x%x", flags);
+    const bool on_device = (flags & PPG_LOGP_STEP_ON_DEVICE) != 0;
+    if (on_device && !step) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: PPG_LOGP_STEP_ON_DEVICE with a NULL address");
+    if (!on_device && step >= (uint64_t)st->horizon)
+        return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: step %llu outside [0, %d)", (unsigned long long)step, st->horizon);
+    if (!logits[0] && !logits[1]) return PPG_OK;   // both species skipped
+    if (!h->logp_off_dev) {
+        const int rc = backend_alloc(h, (void **)&h->logp_off_dev, (size_t)h->batch * 2 * sizeof(int32_t));
+        if (rc != PPG_OK) return rc;
+    }
+    ppg::LogpParams K;
+    memset(&K, 0, sizeof K);
+    K.batch = h->batch; K.S = h->base.S; K.cap_pred = h->base.cap_pred; K.cap_prey = h->base.cap_prey;
+    K.T = st->horizon; K.step_on_device = on_device;
+    K.step = on_device ? 0 : (int32_t)step;
+    K.step_dev = on_device ? (const int32_t *)(uintptr_t)step : nullptr;
+    K.env_state = h->bufs.env_state;
+    for (int s = 0; s < 2; ++s) {
+        K.logits[s] = logits[s]; K.n_actions[s] = out->n_actions[s]; K.capacity[s] = st->capacity[s];
+        K.logp[s] = out->logp[s]; K.entropy[s] = out->entropy[s]; K.dist[s] = (uint32_t *)out->dist[s];
+    }
+    K.slot = st->slot; K.actions = actions; K.off = h->logp_off_dev;
+    return backend_record_logp(h, K, stream);
 }
 
 int ppg_backward(ppg_handle *h, int32_t n_steps, const double *reward, const int16_t *next_row, const uint8_t *in_use,

@@ -248,22 +248,40 @@ class FusedPolicy:
         h = self._handles[species]
         return int(self._lib.ppg_policy_macs_per_observation(h)) if h else 0
 
-    def act(self, envs, actions=None, sample=False, seed=0, want_logits=False, stream=None):
+    def act(self, envs, actions=None, sample=False, seed=0, want_logits=False, stream=None, logits=None):
         """Actions for every row in use of `envs` (a BatchedPredPreyGrass or a list of sub-batches of one GPU), written into
         each env's `.actions` tensor (or the given list of int8 [B_k, S] tensors).  Stream-ordered like a step: launch it on
         a stream that is ordered behind the envs' last step.  want_logits: also return (logits_pred, logits_prey) float32
         [rows in use, n_actions] in env-major row order -- sized for the row capacity, the caller slices by the counts.
         seed: an int, or a one-element int64 tensor on the device -- the kernel then reads the Philox key from it when it RUNS
-        (`PPG_POLICY_SEED_ON_DEVICE`): what a step captured into a HIP graph needs (`GraphedPolicyStep`)."""
+        (`PPG_POLICY_SEED_ON_DEVICE`): what a step captured into a HIP graph needs (`GraphedPolicyStep`).
+        logits: (logits_pred, logits_prey), caller-owned float32 [sum of B_k * capacity_s, n_actions] tensors the kernels write the
+        logits into (either may be None: not wanted for that species).  The call then allocates and zero-fills nothing -- rows behind
+        the rows in use keep what they held -- and returns the pair: what a captured step needs (`trajectory.GraphedCollector`,
+        `env.record_logp()`)."""
         envs = list(envs) if isinstance(envs, (list, tuple)) else [envs]
         acts = [e.actions for e in envs] if actions is None else list(actions)
         n = len(envs)
         aptr = (C.c_void_p * n)(*[e._tensor_arg("actions", a, (torch.int8,), (e.batch_size, e.S)) for e, a in zip(envs, acts)])
         handles = (C.c_void_p * n)(*[e._handle for e in envs])
         lg = [None, None]
-        if want_logits:
-            def cap(t):
-                return sum(e.batch_size * (e.prey_capacity if t else e.pred_capacity) for e in envs)
+
+        def cap(t):
+            return sum(e.batch_size * (e.prey_capacity if t else e.pred_capacity) for e in envs)
+        if logits is not None:
+            if len(logits) != 2:
+                raise ValueError("logits must be the pair (logits_pred, logits_prey); either may be None")
+            for t, (x, net) in enumerate(zip(logits, self.nets)):
+                if x is None:
+                    continue
+                if net is None:
+                    raise ValueError(f"logits[{t}] was given but the policy has no network for that species")
+                shape = (cap(t), net.n_actions)
+                if x.dtype != torch.float32 or tuple(x.shape) != shape or x.device != self.device or not x.is_contiguous():
+                    raise ValueError(f"logits[{t}] must be a contiguous torch.float32 tensor [{shape[0]},{shape[1]}] on {self.device}, not a"
+                                     f"{'' if x.is_contiguous() else ' non-contiguous'} {x.dtype} tensor {list(x.shape)} on {x.device}")
+                lg[t] = x
+        elif want_logits:
             # zero-filled on the stream the kernels run on, so that the fill cannot race with their writes
             lg = _alloc_on(self.device, stream, lambda: [None if net is None else torch.zeros(
                 (cap(t), net.n_actions), dtype=torch.float32, device=self.device) for t, net in enumerate(self.nets)])
@@ -282,7 +300,7 @@ class FusedPolicy:
             if rc == -1:
                 raise ValueError(msg)
             raise RuntimeError(f"ppg_policy_act failed ({rc}): {msg}")
-        return (lg[0], lg[1]) if want_logits else None
+        return (lg[0], lg[1]) if want_logits or logits is not None else None
 
     def close(self):
         for h in self._handles:

@@ -55,6 +55,25 @@ nothing read back, so it replays inside GraphedCollector's graph).  The slot a r
 `action[k]` is the action taken FROM the observation in slot k; it is written by the record() one step later, so the samples of the
 last recorded step (and of rows whose env was not stepped again) hold `_abi.ACTION_UNSET`.  Rows that no longer fit the store are
 dropped whole and counted (`store.counts()`).
+
+What the BEHAVIOUR policy thought of every sample -- log pi_old(a|o) for PPO's ratio, the entropy, the logits for a KL term -- is stored
+in the same slots on request: `logp=(A_pred, A_prey)`.  It cannot be recomputed from the stored observations: `FusedPolicy.act()` draws
+the actions from the float32 logits of its bf16 matrix-core kernels, which differ from a float32 `PolicyNet` forward,
+so a learner that recomputes them starts its first epoch with a ratio that is not 1.  `record_policy(logits)` stands between `act` and
+`step` (`env.record_logp()`, `ppg_record_logp`, csrc/ppg_logp.h: two launches, float64 arithmetic rounded once, nothing read back):
+
+    traj = AgentTrajectories(env, horizon=T, obs_rows=rows, logp=(A_pred, A_prey))
+    bufs = (torch.zeros((B * env.pred_capacity, A_pred), device=dev), torch.zeros((B * env.prey_capacity, A_prey), device=dev))
+    env.step(first_actions); traj.record(first_actions)
+    for t in range(1, T):
+        fused.act(env, sample=True, seed=seed + t, logits=bufs)     # actions into env.actions, logits into bufs
+        traj.record_policy(bufs)                                    # logp / entropy / dist of the samples of the last record()
+        env.step(env.actions); traj.record(env.actions)
+    logp, entropy, dist = traj.behaviour(PREY)                      # [n], [n] or None, [n,A] or None: NaN where no policy was recorded
+    values = traj.scatter(v_pred, v_prey)                           # a critic's per-sample values back into [len,B,S] for gae()
+
+and the closed loop replays as one HIP graph: `GraphedCollector(env, traj, act=lambda: fused.act(env, sample=True, seed=seed_tensor,
+logits=bufs), logits=bufs)`.  The samples of the last recorded step keep NaN until a further act + record_policy() covers them.
 """
 from __future__ import annotations
 
@@ -68,9 +87,12 @@ class ObservationStore:
     `sample[s]` int32 [rows[s]] -- the flat index (t * B + b) * S + r of the row in slot k -- and `action[s]` int8 [rows[s]] (None
     with actions=False); `slot` int32 [T,B,S], the slot of every row of every step or -1; `cursor` int64 [4] on the device: rows stored
     {pred, prey}, rows dropped {pred, prey}.  dtype: the env's observation dtype (default), or torch.float32 on a float64 env -- the
-    rows are then rounded to float32 as they are stored."""
+    rows are then rounded to float32 as they are stored.
+    logp=(A_pred, A_prey): the store also keeps what the behaviour policy thought of every sample (`record_logp()`): `logp[s]` float32
+    [rows[s]], `entropy[s]` likewise (entropy=True) and `dist[s]` float32 [rows[s], A_s], the logits (dist=True); `logp` and `entropy`
+    hold NaN in every slot no policy was recorded for.  Without it the three are None."""
 
-    def __init__(self, env, horizon, rows, dtype=None, actions=True):
+    def __init__(self, env, horizon, rows, dtype=None, actions=True, logp=None, entropy=True, dist=False):
         self.env, self.horizon = env, int(horizon)
         self.capacity = (int(rows[0]), int(rows[1]))
         if self.horizon < 1 or min(self.capacity) < 0:
@@ -86,10 +108,25 @@ class ObservationStore:
         self.action = [torch.full((n,), _abi.ACTION_UNSET, dtype=torch.int8, device=dev) for n in self.capacity] if actions else None
         self.slot = torch.full((self.horizon, env.batch_size, env.S), -1, dtype=torch.int32, device=dev)
         self.cursor = torch.zeros((4,), dtype=torch.int64, device=dev)
+        self.n_actions = self.logp = self.entropy = self.dist = None
+        if logp is not None:
+            self.n_actions = (int(logp[0]), int(logp[1]))
+            if not all(1 <= a <= 32 for a in self.n_actions):
+                raise ValueError(f"logp = {self.n_actions}: the action counts must be in 1..32")
+            self.logp = [torch.full((n,), float("nan"), dtype=torch.float32, device=dev) for n in self.capacity]
+            if entropy:
+                self.entropy = [torch.full((n,), float("nan"), dtype=torch.float32, device=dev) for n in self.capacity]
+            if dist:
+                self.dist = [torch.zeros((n, a), dtype=torch.float32, device=dev) for n, a in zip(self.capacity, self.n_actions)]
 
     def clear(self):
-        """Start filling from slot 0 again (the tensors keep their bytes: everything below the cursor is rewritten as it moves)."""
+        """Start filling from slot 0 again (the tensors keep their bytes: everything below the cursor is rewritten as it moves; `logp`
+        and `entropy`, which are written one call later and only where a policy acted, are refilled with NaN)."""
         self.cursor.zero_()
+        for xs in (self.logp, self.entropy):
+            if xs is not None:
+                for x in xs:
+                    x.fill_(float("nan"))
         return self
 
     def counts(self):
@@ -100,6 +137,47 @@ class ObservationStore:
     def record(self, t, actions=None, stream=None):
         """env.record_obs() into this store."""
         self.env.record_obs(self, t, actions if self.action is not None else None, f32=self.f32, stream=stream)
+        return self
+
+    def record_logp(self, t, logits, actions=None, stream=None):
+        """env.record_logp() into this store: t is the step the env's current output was recorded as (or the device word, which names
+        the next one), logits the pair `FusedPolicy.act(..., logits=...)` filled."""
+        self.env.record_logp(self, t, logits, actions, stream=stream)
+        return self
+
+    def record_logp_torch(self, t, logits, actions=None):
+        """record_logp(t, logits, actions) as torch ops: the same result (float64 arithmetic rounded once; `dist` the same bits),
+        `nonzero`-based, so the host waits for the device at every call (timing baseline, fallback).  t: an int."""
+        env, t = self.env, int(t)
+        if self.logp is None:
+            raise ValueError("the store keeps no log-probabilities: ObservationStore(..., logp=(A_pred, A_prey))")
+        if not 0 <= t < self.horizon:
+            raise ValueError(f"t = {t} is outside [0, {self.horizon})")
+        dev = env.device
+        actions = env.actions if actions is None else actions
+        for s, (first, cap, word) in enumerate(((0, env.pred_capacity, _abi.ENV_N_PRED_ROWS),
+                                                (env.pred_capacity, env.prey_capacity, _abi.ENV_N_PREY_ROWS))):
+            if logits[s] is None:
+                continue
+            A = self.n_actions[s]
+            n = env.env_state[:, word:word + 1].clamp(0, cap)
+            b, j = (torch.arange(cap, device=dev).unsqueeze(0) < n).nonzero(as_tuple=True)   # env-major, rows ascending: the logits' order
+            k = self.slot[t][b, first + j].long()
+            ok = (k >= 0) & (k < self.capacity[s])
+            row, k, a = logits[s][:b.numel()][ok], k[ok], actions[b, first + j][ok].long()
+            d = row.double() - row.double().max(dim=1, keepdim=True).values
+            masked = d == float("-inf")
+            e = torch.where(masked, torch.zeros_like(d), d.exp())
+            total = e.sum(dim=1)
+            w = torch.where(masked, torch.zeros_like(d), e * d).sum(dim=1)
+            ls = total.log()
+            valid = (a >= 0) & (a < A)
+            lp = d.gather(1, a.clamp(0, A - 1).unsqueeze(1)).squeeze(1) - ls
+            self.logp[s][k] = torch.where(valid, lp, torch.full_like(lp, float("nan"))).float()
+            if self.entropy is not None:
+                self.entropy[s][k] = (ls - w / total).float()
+            if self.dist is not None:
+                self.dist[s][k] = row
         return self
 
     def record_obs_torch(self, t, actions=None):
@@ -136,7 +214,7 @@ class ObservationStore:
 
 
 class AgentTrajectories:
-    def __init__(self, env, horizon, step_on_device=False, obs_rows=None):
+    def __init__(self, env, horizon, step_on_device=False, obs_rows=None, logp=None, entropy=True, dist=False):
         self.env = env
         self.horizon = int(horizon)
         if self.horizon < 1:
@@ -156,7 +234,10 @@ class AgentTrajectories:
         self._t = 0
         # obs_rows = (n_pred, n_prey): record() also appends the observation rows in use (and the actions it is given) to a compact
         # store of that many rows per species -- `store`, read through samples() and flat()
-        self.store = ObservationStore(env, self.horizon, obs_rows) if obs_rows is not None else None
+        # logp = (A_pred, A_prey): the store also keeps the behaviour policy's log-probabilities (record_policy(), behaviour())
+        if logp is not None and obs_rows is None:
+            raise ValueError("logp needs a store: AgentTrajectories(..., obs_rows=(n_pred, n_prey), logp=(A_pred, A_prey))")
+        self.store = ObservationStore(env, self.horizon, obs_rows, logp=logp, entropy=entropy, dist=dist) if obs_rows is not None else None
 
     @property
     def t(self):
@@ -207,6 +288,52 @@ class AgentTrajectories:
             self.store.record(self._t, actions)
         self._t += 1
         return self
+
+    def record_policy(self, logits, actions=None):
+        """Store what the behaviour policy thought of the samples of the LAST record(): call it between `fused.act(env, ...,
+        logits=logits)` and the `env.step()` that uses those actions.  logits: the pair act() filled (either may be None); actions:
+        the tensor it wrote (default `env.actions`).  Two launches (`env.record_logp()`), nothing read back.  The step is t - 1 on the
+        host, or `t_dev` with step_on_device -- the kernels subtract the one themselves; before the first record() and past the
+        horizon nothing is written."""
+        if self.store is None or self.store.logp is None:
+            raise RuntimeError("record_policy() needs AgentTrajectories(..., obs_rows=(n_pred, n_prey), logp=(A_pred, A_prey))")
+        if self.step_on_device:
+            self.store.record_logp(self.t_dev, logits, actions)
+        elif self._t > 0:
+            self.store.record_logp(self._t - 1, logits, actions)
+        return self
+
+    def behaviour(self, species):
+        """(logp[:n], entropy[:n] or None, dist[:n] or None) of one species, in the order of samples(): float32 [n], [n] and
+        [n, A_s] (one read-back of the cursor).  NaN in logp / entropy where no policy was recorded for a sample."""
+        if self.store is None or self.store.logp is None:
+            raise RuntimeError("behaviour() needs AgentTrajectories(..., obs_rows=(n_pred, n_prey), logp=(A_pred, A_prey))")
+        st = self.store
+        n = int(st.cursor[species].item())
+        return (st.logp[species][:n], None if st.entropy is None else st.entropy[species][:n],
+                None if st.dist is None else st.dist[species][:n])
+
+    def scatter(self, x_pred, x_prey, fill=0.0):
+        """The inverse of flat(): a [len,B,S] tensor with x_s[k] at the (t, b, r) of sample k of species s and `fill` everywhere else --
+        what brings a critic's per-sample values into the layout gae() takes.  x_pred / x_prey: [n_s] tensors of one dtype in sample
+        order (either may be None).  Plain torch index ops, one read-back of the cursor."""
+        if self.store is None:
+            raise RuntimeError("scatter() needs a store: AgentTrajectories(..., obs_rows=(n_pred, n_prey))")
+        given = [x for x in (x_pred, x_prey) if x is not None]
+        if not given:
+            raise ValueError("scatter() needs at least one of x_pred, x_prey")
+        n_steps, cursor = self.t, self.store.cursor.tolist()
+        B, S = self.reward.shape[1:]
+        out = torch.full((n_steps, B, S), fill, dtype=given[0].dtype, device=self.reward.device)
+        flat = out.reshape(-1)
+        for s, x in enumerate((x_pred, x_prey)):
+            if x is None:
+                continue
+            n = cursor[s]
+            if tuple(x.shape) != (n,) or x.dtype != out.dtype:
+                raise ValueError(f"x of species {s} must be a {out.dtype} tensor [{n}] (the samples stored), not {x.dtype} {list(x.shape)}")
+            flat[self.store.sample[s][:n].long()] = x.to(out.device)
+        return out
 
     def record_obs_torch(self, actions=None):
         """record(actions) of a trajectory with a store as torch ops: record_torch() plus ObservationStore.record_obs_torch() -- the
@@ -348,21 +475,41 @@ class GraphedCollector:
 
         traj.clear(); env.step(...); traj.record()      # eager: this record links nothing and takes the fresh snapshot
 
-    before the next replay(); a replay right after a reset would link the new rows to the old episode's snapshot."""
+    before the next replay(); a replay right after a reset would link the new rows to the old episode's snapshot.
 
-    def __init__(self, env, traj, act=None, auto_reset=True):
+    logits: the (logits_pred, logits_prey) buffers `act` fills, for a trajectory with `logp=`: the body becomes act,
+    `traj.record_policy(logits, env.actions)`, step, record -- the closed loop of a PPO collector, still one linear chain:
+
+        bufs = (torch.zeros((B * env.pred_capacity, A), device=dev), torch.zeros((B * env.prey_capacity, A), device=dev))
+        traj = AgentTrajectories(env, T, step_on_device=True, obs_rows=rows, logp=(A, A))
+
+        def act():
+            fused.act(env, sample=True, seed=seed_tensor, logits=bufs)
+            seed_tensor.add_(1)
+        loop = GraphedCollector(env, traj, act=act, logits=bufs)
+        loop.replay(T - 1)
+        logp, entropy, dist = traj.behaviour(PREY)
+
+    The warm pass acts on an output no record() has stored, so its record_policy() writes nothing; replay i stores the policy of
+    step i - 1, and the samples of the last recorded step keep NaN."""
+
+    def __init__(self, env, traj, act=None, auto_reset=True, logits=None):
         if not getattr(traj, "step_on_device", False):
             raise ValueError("GraphedCollector needs AgentTrajectories(..., step_on_device=True)")
         if traj.env is not env:
             raise ValueError("traj records another env")
         if env.device.type != "cuda":
             raise RuntimeError("GraphedCollector captures a HIP graph: the env must be on a GPU")
+        if logits is not None and act is None:
+            raise ValueError("logits are what `act` fills: GraphedCollector(env, traj, act=..., logits=...)")
         self.env, self.traj = env, traj
         dev = env.device
 
         def body():
             if act is not None:
                 act()
+                if logits is not None:   # (the samples of the previous record(); in the warm pass of an empty trajectory: nothing)
+                    traj.record_policy(logits, env.actions)
                 env.step(env.actions, auto_reset=auto_reset)
                 traj.record(env.actions)   # (a trajectory with a store keeps them as the actions of the previous step's samples)
             else:
