@@ -658,6 +658,57 @@ int ppg_backward(ppg_handle *h, int32_t n_steps, const double *reward, const int
                  const uint8_t *terminated, const uint8_t *truncated, const void *values, int32_t values_dtype, /* values may be NULL */
                  double gamma, double lam, double *returns, double *advantages, void *stream);
 
+/* ---- returns and advantages straight into sample order -----------------------------------------------------------------
+ * ppg_backward_samples is ppg_backward for a learner whose minibatch is indexed by the slots of ppg_record_obs: it READS the critic's
+ * values per sample (values[s][k]) and WRITES advantages and returns per sample (advantage[s][k], returns[s][k], float32), and on
+ * request the per-env moments that advantage normalisation needs -- in ONE launch (one wavefront per env; csrc/ppg_backward.h), with
+ * no [n_steps,B,S] tensor of values, returns or advantages anywhere.  It is defined to equal: scatter the values into [n_steps,B,S]
+ * with 0 elsewhere, ppg_backward, pick the stored rows, round once to float32.  reward, next_row, in_use, terminated, truncated are
+ * ppg_backward's tensors, contiguous device [n_steps,B,S]; st->slot is the int32 [st->horizon,B,S] table ppg_record_obs filled, of which
+ * the first n_steps steps are read; B, S and pred_capacity (cp) are the handle's; s = 0 predators, 1 prey.
+ *   Rows     for every (t, b, r) with t < n_steps: s = r < cp ? 0 : 1, k = st->slot[t][b][r],
+ *              stored = in_use[t][b][r] && 0 <= k && k < st->capacity[s]
+ *            (k is read from memory: it is compared before it becomes an address, a word outside is never followed).
+ *   Values   V[t][b][r] = stored && values[s] ? widen(values[s][k]) : 0.0 -- float64 as it is (PPG_F64) or float32 widened exactly
+ *            (PPG_F32), one dtype for both species.  A selection, never a multiplication: values[s][k] of a slot no stored row
+ *            refers to is not even read, so a NaN there reaches no output.  values[s] == NULL: V = 0 for every row of that species.
+ *   G, A     exactly the recursion of ppg_backward over reward, next_row, the flags and that V, unchanged: the same `has`
+ *            condition, one IEEE float64 operation per line in the same order, no fused multiply-add, gamma * lam formed once in
+ *            double on the host, a next_row outside [0, S) means no successor, the last step (t = n_steps - 1) has no successor.
+ *   Stores   if stored: advantage[s][k] = (float)A[t][b][r] and returns[s][k] = (float)G[t][b][r] -- ONE rounding to nearest even, at
+ *            the store.  Rows in use that the store dropped (slot -1, or a slot word outside the capacity) still take part in the
+ *            recursion with V = 0 -- their successors and predecessors see them exactly as after the scatter with 0 -- and nothing
+ *            is stored for them.  No other element of any output is written: not the slots at or above the cursor, not the slots of
+ *            steps >= n_steps.  If two rows carry the same valid k (a corrupt slot tensor) one of the two values lands there and no
+ *            address leaves the tensors.
+ *   Outputs  advantage[] and returns[] are pairs: both pointers NULL or both set, and not both pairs NULL.  With advantage[] NULL
+ *            the values are not read at all (returns do not depend on V).
+ *   stats    (optional, needs advantage[]) float64 [B,2,3]: per env b and species s {count, sum A, sum A * A} over the stored rows, A
+ *            being the float64 value BEFORE its rounding, in a fixed order so that it can be checked bit for bit: lane l of the
+ *            env's wavefront owns rows 64q + l (cp is a multiple of 64: the species is uniform per q) and keeps three float64
+ *            accumulators per species, started at +0.0; for t = n_steps-1 .. 0 and q ascending, if stored:
+ *              n = n + 1.0;  sum = sum + A;  p = A * A;  sq = sq + p          (each one operation)
+ *            then for m in 1, 2, 4, 8, 16, 32: x = x + x_of_lane(l ^ m) for each of the three (commutative: every lane ends with the
+ *            same bits), and lane 0 stores stats[b][s][0..3).  All B * 2 * 3 elements are written.  The sum over the envs is the
+ *            caller's: one reduction over [B].
+ *   Not read st->obs, sample, action and cursor (they may be NULL); st->horizon only bounds n_steps and sizes slot.
+ * PPG_EINVAL (text in ppg_last_error beginning "ppg_backward_samples:", nothing is launched): n_steps < 1 or n_steps > st->horizon; a
+ * NULL input tensor; st, tg or st->slot NULL; a capacity < 0 or above INT32_MAX; horizon * B * S above INT32_MAX; only one pointer of
+ * an output pair set; both output pairs NULL; stats without advantage[]; a values_dtype that is neither code (checked only if a
+ * values pointer is set); a handle whose S is not 64 * (2 .. 6).
+ * No atomics anywhere in the call.  It touches no env state and no library-owned buffer.  Asynchronous on `stream`. */
+typedef struct ppg_sample_targets {
+    const void *values[2];    /* [st->capacity[s]] per-sample critic values, float32 (PPG_F32) or float64 (PPG_F64);
+                                 NULL: V = 0 for every row of that species */
+    float  *advantage[2];     /* [st->capacity[s]]; both NULL or both set */
+    float  *returns[2];       /* [st->capacity[s]]; both NULL or both set; not both pairs NULL */
+    double *stats;            /* [B,2,3] {count, sum A, sum A*A} per env and species, or NULL; needs advantage[] */
+} ppg_sample_targets;
+int ppg_backward_samples(ppg_handle *h, int32_t n_steps, const double *reward, const int16_t *next_row,
+                         const uint8_t *in_use, const uint8_t *terminated, const uint8_t *truncated,
+                         const ppg_obs_store *st, const ppg_sample_targets *tg, int32_t values_dtype,
+                         double gamma, double lam, void *stream);
+
 /* ---- policy inference next to the env (base_environment/tune_ppo_base_environment.py:106-141) ----------
  * The reference trains two PPO policies (predator_policy / prey_policy) with RLlib's DefaultPPOTorchRLModule and
  * model_config {conv_filters [[16,[3,3],1],[32,[3,3],1],[64,[3,3],1]], fcnet_hiddens [256,256], fcnet_activation relu}.

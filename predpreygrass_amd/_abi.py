@@ -151,6 +151,11 @@ class PpgLogpStore(C.Structure):
     _fields_ = [("logp", C.c_void_p * 2), ("entropy", C.c_void_p * 2), ("dist", C.c_void_p * 2), ("n_actions", C.c_int32 * 2)]
 
 
+class PpgSampleTargets(C.Structure):
+    """include/ppg.h: struct ppg_sample_targets (per-sample values in, advantages / returns / per-env moments out)."""
+    _fields_ = [("values", C.c_void_p * 2), ("advantage", C.c_void_p * 2), ("returns", C.c_void_p * 2), ("stats", C.c_void_p)]
+
+
 class PpgInitState(C.Structure):
     """include/ppg.h: struct ppg_init_state (host uint16 arrays, cells as (x << 8) | y)."""
     _fields_ = [("pred_xy", C.c_void_p), ("prey_xy", C.c_void_p), ("grass_xy", C.c_void_p), ("episode", C.c_uint32), ("reserved_", C.c_uint32)]
@@ -188,7 +193,7 @@ EXPORTED_SYMBOLS = [
     "ppg_get_wave_plan", "ppg_rebalance", "ppg_set_resident_envs", "ppg_get_resident_envs",
     "ppg_export_grid", "ppg_walls_changed", "ppg_state_bytes", "ppg_export_state", "ppg_import_state", "ppg_pack_bytes", "ppg_pack",
     "ppg_fetch_bytes", "ppg_fetch", "ppg_link", "ppg_record", "ppg_record_obs", "ppg_record_logp", "ppg_backward",
-    "ppg_lexkey", "ppg_lds_bytes", "ppg_step_kernel_name", "ppg_last_error",
+    "ppg_backward_samples", "ppg_lexkey", "ppg_lds_bytes", "ppg_step_kernel_name", "ppg_last_error",
 ] + POLICY_SYMBOLS + SPREAD_SYMBOLS
 
 
@@ -262,6 +267,10 @@ def bind(lib: C.CDLL) -> C.CDLL:
     lib.ppg_backward.restype = C.c_int
     lib.ppg_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,   # handle, n_steps, five inputs
                                  C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]   # values, dtype, gamma, lam, G, A, stream
+    lib.ppg_backward_samples.restype = C.c_int
+    lib.ppg_backward_samples.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,   # handle, n_steps, five inputs
+                                         C.POINTER(PpgObsStore), C.POINTER(PpgSampleTargets), C.c_int32, C.c_double, C.c_double,
+                                         C.c_void_p]   # st, tg, dtype, gamma, lam, stream
     if hasattr(lib, "ppg_alloc_spread"):
         lib.ppg_alloc_spread.restype = C.c_int
         lib.ppg_alloc_spread.argtypes = [C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]

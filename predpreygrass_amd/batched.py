@@ -605,6 +605,66 @@ class BatchedPredPreyGrass:
                                            float(gamma), float(lam), ptr(G), ptr(A), self._stream(stream)), "ppg_backward")
         return G, A
 
+    def backward_samples(self, store, reward, next_row, in_use, terminated, truncated, gamma, lam=1.0, values=(None, None),
+                         advantages=True, returns=True, stats=False, stream=None):
+        """backward() from and into SAMPLE order, in ONE launch (`ppg_backward_samples`, include/ppg.h: the recursion, the rows stored
+        and the order of the sums are stated there): the critic's values are read per sample, `values[s][k]` of slot k of species s
+        through `store.slot`, and the advantage and return of every stored row are written to its slot, rounded once to float32.
+        store: a `trajectory.ObservationStore`, or any object with `horizon` (>= T), `capacity` (n_pred, n_prey) and `slot` int32
+        [horizon,B,S]; nothing else of it is looked at.  reward ... truncated: backward()'s [T,B,S] tensors.
+        values: (v_pred, v_prey), float64 or float32 [rows >= capacity[s]] of ONE dtype; None: V = 0 for that species.
+        Returns (advantages, returns, stats): two pairs of float32 [capacity[s]] tensors (None where not asked for), newly allocated
+        and zero in every slot no stored row of the T steps has; stats (stats=True, needs advantages): float64 [B,2,3], per env and
+        species {count, sum A, sum A * A} over the stored rows from the unrounded float64 A -- `stats.sum(0)` are the batch's.
+        stream (optional): as in backward() -- the launch and the allocation of the outputs go to that stream."""
+        if not returns and not advantages:
+            raise ValueError("backward_samples: neither returns nor advantages asked for")
+        if stats and not advantages:
+            raise ValueError("backward_samples: stats need advantages")
+        if len(values) != 2:
+            raise ValueError("values must be the pair (v_pred, v_prey); either may be None")
+        shape = self._trajectory_args(reward=reward, next_row=next_row, in_use=in_use, terminated=terminated, truncated=truncated)
+        horizon, B, S = int(store.horizon), self.batch_size, self.S
+        if shape[0] > horizon:
+            raise ValueError(f"{shape[0]} steps, but the store's horizon is {horizon}")
+        st, tg = _abi.PpgObsStore(), _abi.PpgSampleTargets()
+        st.horizon = horizon
+        st.slot = self._tensor_arg("store.slot", store.slot, (torch.int32,), (horizon, B, S)).value
+        given = [v for v in values if v is not None]
+        if any(v.dtype != given[0].dtype for v in given):
+            raise ValueError("values of the two species must have one dtype")
+        capacity = [int(c) for c in store.capacity]
+        for s, v in enumerate(values):
+            if capacity[s] < 0:
+                raise ValueError(f"store.capacity[{s}] = {capacity[s]} < 0")
+            st.capacity[s] = capacity[s]
+            if v is not None:
+                ptr = self._tensor_arg(f"values[{s}]", v, self._TRAJECTORY_DTYPES["values"], (None,))
+                if v.shape[0] < capacity[s]:
+                    raise ValueError(f"values[{s}] has {v.shape[0]} elements, fewer than the capacity {capacity[s]}")
+                tg.values[s] = ptr.value or st.slot   # (an empty tensor has no address: capacity 0, nothing is addressed through it)
+
+        def outputs():
+            pair = lambda: [torch.zeros((n,), dtype=torch.float32, device=self.device) for n in capacity]
+            return (pair() if advantages else None, pair() if returns else None,
+                    torch.empty((B, 2, 3), dtype=torch.float64, device=self.device) if stats else None)
+        adv, ret, moments = _alloc_on(self.device, stream, outputs)
+        for s in (0, 1):
+            if adv is not None:
+                tg.advantage[s] = adv[s].data_ptr() or st.slot
+            if ret is not None:
+                tg.returns[s] = ret[s].data_ptr() or st.slot
+        if moments is not None:
+            tg.stats = moments.data_ptr()
+
+        def ptr(x):
+            return C.c_void_p(x.data_ptr())
+        self._check(self._lib.ppg_backward_samples(self._handle, shape[0], ptr(reward), ptr(next_row), ptr(in_use), ptr(terminated),
+                                                   ptr(truncated), C.byref(st), C.byref(tg),
+                                                   _abi.F32 if given and given[0].dtype == torch.float32 else _abi.F64,
+                                                   float(gamma), float(lam), self._stream(stream)), "ppg_backward_samples")
+        return adv, ret, moments
+
     def export_grid(self):
         """grid_world_state of every env: float64 [B,4,G,G] (predpreygrass_rllib_env.py:124)."""
         G = self.grid_size

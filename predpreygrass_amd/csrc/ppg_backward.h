@@ -138,4 +138,180 @@ PPG_DEVICE void backward_main(const KP &K, unsigned char *lds) {
     }
 }
 
+// ---- ppg_backward_samples of include/ppg.h: the same recursion, read and written in SAMPLE order ---------------------------------
+// V of a row is gathered from the per-sample values through the slot table of ppg_record_obs (st->slot), and G / A of a stored row are
+// rounded once to float32 and stored at its slot: no [T,B,S] tensor of values, returns or advantages exists.  The recursion is the one
+// of backward_env, line for line (rows the store dropped take part with V = 0); what differs:
+//   - a DEPENDENT load chain: slot[t][b][r] (4 bytes, dense) and then values[s][k] (4 or 8 bytes, scattered).  k is compared with
+//     [0, capacity[s]) before it becomes an address, and a row that is not stored keeps k = -1 from then on.  With PREFETCH both are
+//     requested for step t - 1 with the other inputs, in front of step t's LDS gather -- measured 3 % SLOWER than loading at the top
+//     of the step here (profiles/EXPERIMENTS.md, `ppg_backward_samples`), so the host asks for it only when PPG_BACKWARD_PREFETCH
+//     says so;
+//   - two scattered 4-byte stores per STORED row instead of two dense 8-byte stores per element;
+//   - STATS: three float64 accumulators per species and lane {count, sum A, sum A * A} over the stored rows in the order
+//     include/ppg.h states, reduced by an xor butterfly at the end; lane 0 stores the six doubles of its env.
+// The next_row / in_use / stop words of a row are packed into ONE register (BackwardSampleIn::meta) and `stored` into k's sign, and
+// the species of a row register is a template argument (NP): the six-row instantiation with STATS has to stay free of scratch and
+// within 128 VGPRs, four one-wave workgroups per SIMD (profiles/EXPERIMENTS.md, `ppg_backward_samples`).
+// Ordinary vector loads / stores, LDS accesses and wave shuffles only: no atomics.
+struct BackwardSamplesParams {
+    int32_t batch, S, T;
+    int32_t cap_pred;           // rows [0, cap_pred) are predators (species 0): a multiple of 64
+    int32_t values_f32;         // values[] are float32 (widened exactly) instead of float64
+    int32_t prefetch;           // request step t - 1's inputs before step t's gather
+    int32_t capacity[2];        // slots of each species' store (checked against INT32_MAX on the host)
+    const double *reward;       // [T,B,S]
+    const int16_t *next_row;    // [T,B,S]
+    const uint8_t *in_use, *terminated, *truncated;   // [T,B,S], 0 / 1
+    const int32_t *slot;        // [horizon >= T,B,S]
+    const void *values[2];      // [capacity[s]] float64 / float32, NULL: V = 0
+    double gamma, gl;           // gl = gamma * lam, formed once on the host
+    float *advantage[2];        // [capacity[s]], both NULL or both set
+    float *returns[2];          // [capacity[s]], both NULL or both set (not both pairs NULL)
+    double *stats;              // [B,2,3] or NULL
+};
+
+constexpr uint32_t BACKWARD_META_USED = 0x10000u, BACKWARD_META_STOP = 0x20000u;   // above next_row's 16 bits
+
+// a lane's rows of one step
+template <int NR>
+struct BackwardSampleIn {
+    double rew[NR], v[NR];
+    uint32_t meta[NR];   // next_row (low 16 bits) | BACKWARD_META_USED | BACKWARD_META_STOP
+    int32_t k[NR];       // the row's slot if it is stored (in use, 0 <= slot < capacity[s]), else -1
+};
+
+// NP: the row registers of the predators (pred_capacity / 64), so the species of register q is known when the code is compiled
+template <int NR, int NP, class KP>
+PPG_DEVICE void backward_samples_load(const KP &K, size_t at, int ln, bool want_a, BackwardSampleIn<NR> &in) {
+    int32_t word[NR];
+#pragma unroll
+    for (int q = 0; q < NR; ++q) word[q] = K.slot[at + (size_t)(64 * q + ln)];   // (first: the gather below waits for these)
+#pragma unroll
+    for (int q = 0; q < NR; ++q) {
+        const size_t i = at + (size_t)(64 * q + ln);
+        in.rew[q] = K.reward[i];
+        const uint32_t used = K.in_use[i] != 0, stop = (K.terminated[i] | K.truncated[i]) != 0;
+        in.meta[q] = (uint32_t)(uint16_t)K.next_row[i] | (used ? BACKWARD_META_USED : 0u) | (stop ? BACKWARD_META_STOP : 0u);
+    }
+    const bool f32 = K.values_f32 != 0;   // (wave-uniform)
+#pragma unroll
+    for (int q = 0; q < NR; ++q) {
+        const int sp = q < NP ? 0 : 1;   // (a constant once the loop is unrolled)
+        const int32_t k = word[q];
+        const void *values = K.values[sp];
+        const bool stored = (in.meta[q] & BACKWARD_META_USED) != 0 && k >= 0 && k < K.capacity[sp];
+        in.k[q] = stored ? k : -1;
+        double v = 0.0;
+        if (want_a && stored && values != nullptr) {   // (a selection: an unreferenced slot's word is never loaded)
+            if (f32) v = (double)((const float *)values)[k];
+            else v = ((const double *)values)[k];
+        }
+        in.v[q] = v;
+    }
+}
+
+template <int NR, int NP, bool PREFETCH, bool STATS, class KP>
+PPG_DEVICE void backward_samples_env(const KP &K, unsigned char *lds, int b, int ln) {
+    const int S = 64 * NR, T = K.T;
+    const bool want_g = K.returns[0] != nullptr, want_a = K.advantage[0] != nullptr;
+    const double gamma = K.gamma, gl = K.gl;
+    double *lg = (double *)lds, *la = lg + BACKWARD_MAX_ROWS, *lv = la + BACKWARD_MAX_ROWS;
+    const size_t step = (size_t)K.batch * (size_t)S, env = (size_t)b * (size_t)S;
+    double cnt[2] = {0.0, 0.0}, sum[2] = {0.0, 0.0}, sq[2] = {0.0, 0.0};   // (indexed by constants only: registers)
+    BackwardSampleIn<NR> cur, ahead;
+    if (PREFETCH) backward_samples_load<NR, NP>(K, (size_t)(T - 1) * step + env, ln, want_a, cur);
+    for (int t = T - 1; t >= 0; --t) {
+        const size_t at = (size_t)t * step + env;
+        if (!PREFETCH) backward_samples_load<NR, NP>(K, at, ln, want_a, cur);
+        else if (t > 0) backward_samples_load<NR, NP>(K, at - step, ln, want_a, ahead);
+        double g[NR], a[NR];
+#pragma unroll
+        for (int q = 0; q < NR; ++q) {
+            const int sp = q < NP ? 0 : 1;   // (a constant once the loop is unrolled)
+            const uint32_t meta = cur.meta[q];
+            const int nx = (int)(int16_t)(uint16_t)meta;
+            const bool used = (meta & BACKWARD_META_USED) != 0;
+            const bool has = t + 1 < T && used && (meta & BACKWARD_META_STOP) == 0 && nx >= 0 && nx < S;
+            const int j = has ? nx : 0;   // the only LDS index a tensor's value ever becomes: checked against [0, S) above
+            double g_succ = 0.0, a_succ = 0.0, v_succ = 0.0;
+            if (t + 1 < T) {              // (wave-uniform; the arrays hold nothing yet at the last step)
+                if (want_g) { const double x = lg[j]; g_succ = has ? x : 0.0; }
+                if (want_a) { const double x = la[j], y = lv[j]; a_succ = has ? x : 0.0; v_succ = has ? y : 0.0; }
+            }
+            const double rew = cur.rew[q];
+            const double gm = g_succ * gamma;
+            const double gq = rew + gm;
+            g[q] = used ? gq : 0.0;
+            const double vm = v_succ * gamma;
+            const double boot = rew + vm;
+            const double delta = boot - cur.v[q];
+            const double am = a_succ * gl;
+            const double aq = delta + am;
+            a[q] = used ? aq : 0.0;
+            const int32_t k = cur.k[q];
+            if (k >= 0) {                 // stored: in use and 0 <= k < capacity[s] (backward_samples_load)
+                if (want_g) K.returns[sp][k] = (float)g[q];
+                if (want_a) K.advantage[sp][k] = (float)a[q];
+                if (STATS) {
+                    cnt[sp] = cnt[sp] + 1.0;
+                    sum[sp] = sum[sp] + a[q];
+                    const double p = a[q] * a[q];
+                    sq[sp] = sq[sp] + p;
+                }
+            }
+        }
+        if (t == 0) break;
+        wv::sync();   // every lane has read step t + 1's values
+#pragma unroll
+        for (int q = 0; q < NR; ++q) {
+            const int r = 64 * q + ln;
+            if (want_g) lg[r] = g[q];
+            if (want_a) { la[r] = a[q]; lv[r] = cur.v[q]; }
+        }
+        wv::sync();   // step t's values are there for every lane
+        if (PREFETCH) cur = ahead;
+    }
+    if (STATS) {
+#pragma unroll
+        for (int sp = 0; sp < 2; ++sp) {
+            double x[3] = {cnt[sp], sum[sp], sq[sp]};
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+#pragma unroll
+                for (int m = 1; m < 64; m <<= 1) x[c] = x[c] + wv::shfl_xor_f64(x[c], m);
+                if (ln == 0) K.stats[((size_t)b * 2 + (size_t)sp) * 3 + (size_t)c] = x[c];
+            }
+        }
+    }
+}
+
+template <int NR, int NP, class KP>
+PPG_DEVICE void backward_samples_rows(const KP &K, unsigned char *lds, int b, int ln) {
+    if (K.stats != nullptr) {
+        if (K.prefetch) backward_samples_env<NR, NP, true, true>(K, lds, b, ln);
+        else backward_samples_env<NR, NP, false, true>(K, lds, b, ln);
+    } else {
+        if (K.prefetch) backward_samples_env<NR, NP, true, false>(K, lds, b, ln);
+        else backward_samples_env<NR, NP, false, false>(K, lds, b, ln);
+    }
+}
+
+template <class KP>
+PPG_DEVICE void backward_samples_main(const KP &K, unsigned char *lds) {
+    const int b = PPG_BLOCK_INDEX();
+    if (b >= K.batch) return;
+    const int ln = wv::lane();
+    // the five (pred_capacity, prey_capacity) ppg_create accepts, as 4 * (S / 64) + pred_capacity / 64; like backward_main another
+    // geometry computes nothing rather than run an instantiation whose rows are not the env's
+    switch (K.S / 64 * 4 + K.cap_pred / 64) {
+    case 2 * 4 + 1: backward_samples_rows<2, 1>(K, lds, b, ln); break;   //  64 +  64
+    case 3 * 4 + 1: backward_samples_rows<3, 1>(K, lds, b, ln); break;   //  64 + 128
+    case 4 * 4 + 2: backward_samples_rows<4, 2>(K, lds, b, ln); break;   // 128 + 128
+    case 5 * 4 + 1: backward_samples_rows<5, 1>(K, lds, b, ln); break;   //  64 + 256
+    case 6 * 4 + 2: backward_samples_rows<6, 2>(K, lds, b, ln); break;   // 128 + 256
+    default: break;
+    }
+}
+
 }  // namespace ppg

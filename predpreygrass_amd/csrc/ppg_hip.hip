@@ -341,6 +341,20 @@ static int backend_backward(ppg_handle *h, const ppg::BackwardParams &K, void *s
     return PPG_OK;
 }
 
+// ---- ppg_backward_samples: the same recursion from and into sample order (ppg_backward.h) ------------------------------
+extern "C" __global__ void __launch_bounds__(64) ppg_backward_samples_rows(const ppg::BackwardSamplesParams K) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[ppg::BACKWARD_LDS_BYTES];
+    ppg::backward_samples_main(*PPG_KERNARG_PTR(ppg::BackwardSamplesParams, K), lds);
+}
+
+static int backend_backward_samples(ppg_handle *h, const ppg::BackwardSamplesParams &K, void *stream) {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(ppg_backward_samples_rows, dim3((unsigned)K.batch), dim3(64), 0, (hipStream_t)stream, K);
+    PPG_HIP_TRY(h, hipGetLastError());
+    return PPG_OK;
+}
+
 static int backend_copy(ppg_handle *h, void *dst, const void *src, size_t bytes, bool to_device, void *stream) {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));

@@ -59,6 +59,7 @@ struct ppg_handle {
     int64_t *obs_base_dev;      // library-owned [B,2] slot bases of ppg_record_obs (NULL until first used)
     int32_t *logp_off_dev;      // library-owned [B,2] logits row offsets of ppg_record_logp (NULL until first used)
     int32_t backward_prefetch;  // ppg_backward requests step t - 1's inputs before step t's gather (PPG_BACKWARD_PREFETCH, read at create)
+    int32_t backward_samples_prefetch;   // the same of ppg_backward_samples: off unless PPG_BACKWARD_PREFETCH asks for it
     ppg_config cfg;
     ppg_config_gen2 cfg2;
     int32_t gen2;  // created by ppg_create_gen2
@@ -605,6 +606,17 @@ static int backend_backward(ppg_handle *, const ppg::BackwardParams &K, void *) 
     return PPG_OK;
 }
 #endif
+// the launch of ppg_backward_samples (ppg_backward.h)
+#ifndef PPG_WAVE_EMU
+static int backend_backward_samples(ppg_handle *h, const ppg::BackwardSamplesParams &K, void *stream);
+#else
+// (CPU test build: defined here for the same reason as backend_link)
+static void ppg_backward_samples_entry(void *arg) { ppg::backward_samples_main(*(const ppg::BackwardSamplesParams *)arg, wv::emu().lds); }
+static int backend_backward_samples(ppg_handle *, const ppg::BackwardSamplesParams &K, void *) {
+    for (int b = 0; b < K.batch; ++b) wv::run_block(ppg_backward_samples_entry, (void *)&K, b, ppg::BACKWARD_LDS_BYTES, 1);
+    return PPG_OK;
+}
+#endif
 
 // The state tensors of one env, in image order (include/ppg.h: ppg_state_header): pointer, bytes per env.
 struct ppg_state_field { void *base; size_t bytes; };
@@ -647,6 +659,7 @@ static int ppg_create_common(const ppg_config *cfg, const ppg_config_gen2 *cfg2,
         h->step_lds_pad = pad ? atoi(pad) : 0;
         const char *pf = getenv("PPG_BACKWARD_PREFETCH");   // (A/B of ppg_backward's load placement: profiles/EXPERIMENTS.md)
         h->backward_prefetch = pf ? (atoi(pf) != 0) : 1;
+        h->backward_samples_prefetch = pf ? (atoi(pf) != 0) : 0;   // (ppg_backward_samples: measured slower one step ahead, same record)
         const char *rb = getenv("PPG_RESIDENT_BYTES");
         h->resident_bytes = rb ? atoll(rb) : PPG_RESIDENT_BYTES_DEFAULT;
         if (h->resident_bytes < 0) h->resident_bytes = 0;
@@ -1392,6 +1405,48 @@ int ppg_backward(ppg_handle *h, int32_t n_steps, const double *reward, const int
     K.gamma = gamma; K.gl = gamma * lam;
     K.returns = returns; K.advantages = advantages;
     return backend_backward(h, K, stream);
+}
+
+int ppg_backward_samples(ppg_handle *h, int32_t n_steps, const double *reward, const int16_t *next_row, const uint8_t *in_use,
+                         const uint8_t *terminated, const uint8_t *truncated, const ppg_obs_store *st, const ppg_sample_targets *tg,
+                         int32_t values_dtype, double gamma, double lam, void *stream) {
+    if (!h) return PPG_EINVAL;
+    if (!st || !tg) return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: st or tg is NULL");
+    if (!st->slot) return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: slot of ppg_obs_store is NULL");
+    if (!reward || !next_row || !in_use || !terminated || !truncated)
+        return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: an input pointer is NULL");
+    if (n_steps < 1 || n_steps > st->horizon)
+        return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: n_steps %d outside [1, horizon %d]", n_steps, st->horizon);
+    for (int s = 0; s < 2; ++s)
+        if (st->capacity[s] < 0 || st->capacity[s] > INT32_MAX)
+            return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: capacity[%d] = %lld outside [0, 2^31)", s, (long long)st->capacity[s]);
+    if ((uint64_t)st->horizon * (uint64_t)h->batch * (uint64_t)h->base.S > (uint64_t)INT32_MAX)
+        return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: horizon %d x %d envs x %d rows does not fit the int32 sample index", st->horizon, h->batch, h->base.S);
+    if (!tg->advantage[0] != !tg->advantage[1])
+        return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: only one of the two advantage[] pointers is set");
+    if (!tg->returns[0] != !tg->returns[1])
+        return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: only one of the two returns[] pointers is set");
+    if (!tg->advantage[0] && !tg->returns[0]) return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: advantage[] and returns[] are both NULL");
+    if (tg->stats && !tg->advantage[0]) return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: stats need advantage[]");
+    if ((tg->values[0] || tg->values[1]) && values_dtype != PPG_F64 && values_dtype != PPG_F32)
+        return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: values_dtype %d is neither PPG_F64 nor PPG_F32", values_dtype);
+    const int S = h->base.S;
+    if (S % 64 != 0 || S < 128 || S * 8 * 3 > ppg::BACKWARD_LDS_BYTES)   // the kernel's instantiations: 2 .. 6 row registers per lane
+        return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: %d rows per env (needs a multiple of 64 in 128..%d)", S, ppg::BACKWARD_MAX_ROWS);
+    ppg::BackwardSamplesParams K;
+    memset(&K, 0, sizeof K);
+    K.batch = h->batch; K.S = S; K.T = n_steps; K.cap_pred = h->base.cap_pred;
+    K.values_f32 = values_dtype == PPG_F32; K.prefetch = h->backward_samples_prefetch;
+    K.reward = reward; K.next_row = next_row; K.in_use = in_use; K.terminated = terminated; K.truncated = truncated;
+    K.slot = st->slot;
+    for (int s = 0; s < 2; ++s) {
+        K.capacity[s] = (int32_t)st->capacity[s];
+        K.values[s] = tg->advantage[0] ? tg->values[s] : nullptr;   // (returns alone do not depend on V)
+        K.advantage[s] = tg->advantage[s]; K.returns[s] = tg->returns[s];
+    }
+    K.gamma = gamma; K.gl = gamma * lam;
+    K.stats = tg->stats;
+    return backend_backward_samples(h, K, stream);
 }
 
 #ifdef PPG_PROFILE_PHASES

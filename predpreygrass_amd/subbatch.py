@@ -172,7 +172,8 @@ class SubBatchedPredPreyGrass:
     def link(self):
         """`link()` of every sub-batch on its own stream: a list of (prev_row, next_row), one pair per sub-batch (row numbers are
         per env, so nothing has to be shifted).  `backward()` (returns / GAE over a recorded horizon) is per sub-batch as well: there is
-        none here -- keep one AgentTrajectories per sub-batch, or call `subs[i].backward(..., stream=streams[i])`."""
+        none here -- keep one AgentTrajectories per sub-batch, or call `subs[i].backward(..., stream=streams[i])`.  `backward_samples()`
+        (the same from and into sample order) likewise: `subs[i].backward_samples(store_i, ..., stream=streams[i])`."""
         return [e.link(stream=s) for e, s in zip(self.subs, self.streams)]
 
     def rollout(self, n_steps, random_actions=True, auto_reset=False):

@@ -74,8 +74,21 @@ so a learner that recomputes them starts its first epoch with a ratio that is no
 
 and the closed loop replays as one HIP graph: `GraphedCollector(env, traj, act=lambda: fused.act(env, sample=True, seed=seed_tensor,
 logits=bufs), logits=bufs)`.  The samples of the last recorded step keep NaN until a further act + record_policy() covers them.
+
+The column PPO optimises against -- the advantage, and the return or value target -- comes in the same slots, in one launch
+(`env.backward_samples()`, `ppg_backward_samples`, csrc/ppg_backward.h): the critic's per-sample values are read through `store.slot`,
+the recursion of `ppg_backward` runs in float64, and every stored sample's A and G are rounded once to float32 at its slot.  It gives
+the bits of scatter() -> returns_and_gae() -> flat() -> .float() (kept verbatim as `targets_torch()`) without the three float64
+[len,B,S] tensors that path allocates, writes and reads back to pick a fifth of their elements:
+
+    v_pred, v_prey = critic(traj.samples(PREDATOR)[1]), critic(traj.samples(PREY)[1])   # float32 / float64 [n_s], one value per sample
+    adv, ret, stats = traj.targets(v_pred, v_prey, 0.99, 0.95)      # adv[s], ret[s]: float32 [n_s] in the order of samples(s)
+    count, mean, std = traj.advantage_moments(stats)                # float64 [2] each, no read-back
+    adv_n = (adv[PREY] - mean[PREY]) / (std[PREY] + 1e-8)           # the usual value target: adv[PREY] + v_prey
 """
 from __future__ import annotations
+
+import types
 
 import torch
 
@@ -452,6 +465,86 @@ class AgentTrajectories:
             a_next = torch.where(self.in_use[t], a, zero)
             A[t] = a_next
         return A
+
+    @staticmethod
+    def _sample_values(v, n, s):
+        """A species' per-sample values as targets() / targets_torch() take them: [n], float64 / float32 as they are, any other float
+        dtype through float32 (exact for bfloat16 / float16)."""
+        if v is None:
+            return None
+        if tuple(v.shape) != (n,) or not v.dtype.is_floating_point:
+            raise ValueError(f"the values of species {s} must be a float tensor [{n}] (the samples stored), not {v.dtype} {list(v.shape)}")
+        return v if v.dtype in (torch.float64, torch.float32) else v.to(torch.float32)
+
+    def targets(self, v_pred, v_prey, gamma, lam, returns=True, stats=True):
+        """(adv, ret, stats): the advantage and the discounted return of every stored sample, in the order of samples() -- `adv[s]`,
+        `ret[s]` float32 [n_s] per species s (ret is None with returns=False) -- from the critic's per-sample values v_pred / v_prey
+        ([n_s] each, one dtype; None: V = 0 for that species), over the first len(self) steps.  ONE launch (`env.backward_samples()`,
+        `ppg_backward_samples`): the values are read through `store.slot`, the recursion runs in float64 -- rows the store dropped
+        take part with V = 0 -- and A and G are rounded once to float32 at the sample's slot: the bits of targets_torch(), without a
+        [len,B,S] tensor of values, returns or advantages.  stats (None with stats=False): float64 [B,2,3], per env and species
+        {count, sum A, sum A * A} of the unrounded advantages, for advantage_moments().  One read-back: the store's cursor (with
+        step_on_device the step index comes with it).  An empty trajectory gives empty tensors without a launch."""
+        if self.store is None:
+            raise RuntimeError("targets() needs a store: AgentTrajectories(..., obs_rows=(n_pred, n_prey))")
+        st, dev = self.store, self.reward.device
+        if self.step_on_device:
+            n_pred, n_prey, n = torch.cat((st.cursor[:2], self.t_dev.to(torch.int64))).tolist()   # (the one read-back)
+            n = min(max(n, 0), self.horizon)
+        else:
+            (n_pred, n_prey), n = st.cursor[:2].tolist(), self._t
+        values = [self._sample_values(v, count, s) for s, (v, count) in enumerate(((v_pred, n_pred), (v_prey, n_prey)))]
+        if values[0] is not None and values[1] is not None and values[0].dtype != values[1].dtype:
+            raise ValueError(f"v_pred and v_prey must have one dtype, not {values[0].dtype} and {values[1].dtype}")
+        values = [None if v is None else v.to(dev).contiguous() for v in values]
+        B = self.reward.shape[1]
+        if n == 0:
+            empty = lambda: [torch.zeros((0,), dtype=torch.float32, device=dev) for _ in range(2)]
+            return empty(), (empty() if returns else None), (torch.zeros((B, 2, 3), dtype=torch.float64, device=dev) if stats else None)
+        # (the samples stored so far are the store as far as this call goes: a slot word is compared with n_s, and the outputs are [n_s])
+        view = types.SimpleNamespace(horizon=st.horizon, capacity=(n_pred, n_prey), slot=st.slot)
+        return self.env.backward_samples(view, self.reward[:n], self.next_row[:n], self.in_use[:n], self.terminated[:n],
+                                         self.truncated[:n], gamma, lam, values=values, returns=returns, stats=stats)
+
+    def targets_torch(self, v_pred, v_prey, gamma, lam, returns=True, stats=True):
+        """targets() as the composition it replaces -- scatter() into [len,B,S], returns_and_gae(), flat() per species, .float(): the
+        same bits in adv and ret (timing baseline, fallback).  stats are index_add sums here: the same counts, the sums equal to
+        targets()'s up to the order of the additions."""
+        if self.store is None:
+            raise RuntimeError("targets_torch() needs a store: AgentTrajectories(..., obs_rows=(n_pred, n_prey))")
+        n_steps, cursor = self.t, self.store.cursor.tolist()
+        B, S = self.reward.shape[1:]
+        v_pred, v_prey = (self._sample_values(v, cursor[s], s) for s, v in enumerate((v_pred, v_prey)))
+        if v_pred is None and v_prey is None:
+            values = torch.zeros((n_steps, B, S), dtype=torch.float64, device=self.reward.device)
+        else:
+            values = self.scatter(v_pred, v_prey)
+        G, A = self.returns_and_gae(values, gamma, lam)
+        index = [self.samples(s)[2] for s in (0, 1)]
+        a64 = [A.reshape(-1)[i] for i in index]
+        adv = [a.float() for a in a64]
+        ret = [G.reshape(-1)[i].float() for i in index] if returns else None
+        moments = None
+        if stats:
+            moments = torch.zeros((B, 2, 3), dtype=torch.float64, device=self.reward.device)
+            for s, (i, a) in enumerate(zip(index, a64)):
+                b = (i // S) % B
+                for c, x in enumerate((torch.ones_like(a), a, a * a)):
+                    moments[:, s, c].index_add_(0, b, x)
+        return adv, ret, moments
+
+    @staticmethod
+    def advantage_moments(stats):
+        """(count, mean, std) of the advantages per species -- float64 [2] device tensors, nothing read back -- from the `stats` of
+        targets(): the [B,2,3] sums are added over the envs (`stats.sum(0)`), mean = sum / n, std = sqrt(max(sq / n - mean^2, 0)) (the
+        population variance, clamped at 0 against its own rounding).  A species without a stored sample (n = 0) gets mean 0 and std
+        0: its sums are 0 and they are divided by 1, so no NaN reaches a learner that normalises an empty tensor."""
+        total = stats.sum(0)
+        count = total[:, 0]
+        n = count.clamp_min(1.0)
+        mean = total[:, 1] / n
+        var = (total[:, 2] / n - mean * mean).clamp_min(0.0)
+        return count, mean, var.sqrt()
 
 
 class GraphedCollector:
