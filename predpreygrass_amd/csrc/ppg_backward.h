@@ -58,12 +58,63 @@ PPG_DEVICE void backward_load(const KP &K, size_t at, int ln, bool want_a, Backw
     }
 }
 
+// ---- the recursion both kernels run (ppg_backward and ppg_backward_samples below) -------------------------------------------------
+// what does not change from step to step: the outputs asked for, the discounts, and G | A | V of step t + 1 in LDS
+struct BackwardRec {
+    bool want_g, want_a;
+    double gamma, gl;
+    double *lg, *la, *lv;
+};
+
+template <class KP>
+PPG_DEVICE BackwardRec backward_rec(const KP &K, unsigned char *lds, bool want_g, bool want_a) {
+    BackwardRec R;
+    R.want_g = want_g; R.want_a = want_a; R.gamma = K.gamma; R.gl = K.gl;
+    R.lg = (double *)lds; R.la = R.lg + BACKWARD_MAX_ROWS; R.lv = R.la + BACKWARD_MAX_ROWS;
+    return R;
+}
+
+// One row of step t: G[t] and A[t] from the row's inputs and its successor's values of step t + 1.  more: t + 1 < T (wave-uniform;
+// the arrays hold nothing yet at the last step).  Every line one IEEE float64 operation, in the order of trajectory.py.
+template <int S>
+PPG_DEVICE void backward_row(const BackwardRec &R, bool more, bool used, bool stop, int16_t next, double rew, double v, double &g, double &a) {
+    const int nx = (int)next;
+    const bool has = more && used && !stop && nx >= 0 && nx < S;
+    const int j = has ? nx : 0;   // the only LDS index a tensor's value ever becomes: checked against [0, S) above
+    double g_succ = 0.0, a_succ = 0.0, v_succ = 0.0;
+    if (more) {
+        if (R.want_g) { const double x = R.lg[j]; g_succ = has ? x : 0.0; }
+        if (R.want_a) { const double x = R.la[j], y = R.lv[j]; a_succ = has ? x : 0.0; v_succ = has ? y : 0.0; }
+    }
+    const double gm = g_succ * R.gamma;
+    const double gq = rew + gm;
+    g = used ? gq : 0.0;
+    const double vm = v_succ * R.gamma;
+    const double boot = rew + vm;
+    const double delta = boot - v;
+    const double am = a_succ * R.gl;
+    const double aq = delta + am;
+    a = used ? aq : 0.0;
+}
+
+// step t's values replace step t + 1's in LDS, between two ordering points
+template <int NR>
+PPG_DEVICE void backward_publish(const BackwardRec &R, int ln, const double (&g)[NR], const double (&a)[NR], const double (&v)[NR]) {
+    wv::sync();   // every lane has read step t + 1's values
+#pragma unroll
+    for (int q = 0; q < NR; ++q) {
+        const int r = 64 * q + ln;
+        if (R.want_g) R.lg[r] = g[q];
+        if (R.want_a) { R.la[r] = a[q]; R.lv[r] = v[q]; }
+    }
+    wv::sync();   // step t's values are there for every lane
+}
+
 template <int NR, bool F32, bool PREFETCH, class KP>
 PPG_DEVICE void backward_env(const KP &K, unsigned char *lds, int b, int ln) {
     const int S = 64 * NR, T = K.T;
     const bool want_g = K.returns != nullptr, want_a = K.advantages != nullptr;
-    const double gamma = K.gamma, gl = K.gl;
-    double *lg = (double *)lds, *la = lg + BACKWARD_MAX_ROWS, *lv = la + BACKWARD_MAX_ROWS;
+    const BackwardRec R = backward_rec(K, lds, want_g, want_a);
     const size_t step = (size_t)K.batch * (size_t)S, env = (size_t)b * (size_t)S;
     BackwardIn<NR> cur, ahead;
     if (PREFETCH) backward_load<NR, F32>(K, (size_t)(T - 1) * step + env, ln, want_a, cur);
@@ -74,38 +125,13 @@ PPG_DEVICE void backward_env(const KP &K, unsigned char *lds, int b, int ln) {
         double g[NR], a[NR];
 #pragma unroll
         for (int q = 0; q < NR; ++q) {
-            const int nx = (int)cur.nxt[q];
-            const bool used = cur.used[q] != 0;
-            const bool has = t + 1 < T && used && cur.stop[q] == 0 && nx >= 0 && nx < S;
-            const int j = has ? nx : 0;   // the only index a tensor's value ever becomes: checked against [0, S) above
-            double g_succ = 0.0, a_succ = 0.0, v_succ = 0.0;
-            if (t + 1 < T) {              // (wave-uniform; the arrays hold nothing yet at the last step)
-                if (want_g) { const double x = lg[j]; g_succ = has ? x : 0.0; }
-                if (want_a) { const double x = la[j], y = lv[j]; a_succ = has ? x : 0.0; v_succ = has ? y : 0.0; }
-            }
-            const double rew = cur.rew[q];
-            const double gm = g_succ * gamma;
-            const double gq = rew + gm;
-            g[q] = used ? gq : 0.0;
-            const double vm = v_succ * gamma;
-            const double boot = rew + vm;
-            const double delta = boot - cur.v[q];
-            const double am = a_succ * gl;
-            const double aq = delta + am;
-            a[q] = used ? aq : 0.0;
+            backward_row<S>(R, t + 1 < T, cur.used[q] != 0, cur.stop[q] != 0, cur.nxt[q], cur.rew[q], cur.v[q], g[q], a[q]);
             const size_t i = at + (size_t)(64 * q + ln);
             if (want_g) K.returns[i] = g[q];
             if (want_a) K.advantages[i] = a[q];
         }
         if (t == 0) break;
-        wv::sync();   // every lane has read step t + 1's values
-#pragma unroll
-        for (int q = 0; q < NR; ++q) {
-            const int r = 64 * q + ln;
-            if (want_g) lg[r] = g[q];
-            if (want_a) { la[r] = a[q]; lv[r] = cur.v[q]; }
-        }
-        wv::sync();   // step t's values are there for every lane
+        backward_publish(R, ln, g, a, cur.v);
         if (PREFETCH) cur = ahead;
     }
 }
@@ -140,8 +166,8 @@ PPG_DEVICE void backward_main(const KP &K, unsigned char *lds) {
 
 // ---- ppg_backward_samples of include/ppg.h: the same recursion, read and written in SAMPLE order ---------------------------------
 // V of a row is gathered from the per-sample values through the slot table of ppg_record_obs (st->slot), and G / A of a stored row are
-// rounded once to float32 and stored at its slot: no [T,B,S] tensor of values, returns or advantages exists.  The recursion is the one
-// of backward_env, line for line (rows the store dropped take part with V = 0); what differs:
+// rounded once to float32 and stored at its slot: no [T,B,S] tensor of values, returns or advantages exists.  The recursion is
+// backward_row / backward_publish above (rows the store dropped take part with V = 0); what differs:
 //   - a DEPENDENT load chain: slot[t][b][r] (4 bytes, dense) and then values[s][k] (4 or 8 bytes, scattered).  k is compared with
 //     [0, capacity[s]) before it becomes an address, and a row that is not stored keeps k = -1 from then on.  With PREFETCH both are
 //     requested for step t - 1 with the other inputs, in front of step t's LDS gather -- measured 3 % SLOWER than loading at the top
@@ -215,8 +241,7 @@ template <int NR, int NP, bool PREFETCH, bool STATS, class KP>
 PPG_DEVICE void backward_samples_env(const KP &K, unsigned char *lds, int b, int ln) {
     const int S = 64 * NR, T = K.T;
     const bool want_g = K.returns[0] != nullptr, want_a = K.advantage[0] != nullptr;
-    const double gamma = K.gamma, gl = K.gl;
-    double *lg = (double *)lds, *la = lg + BACKWARD_MAX_ROWS, *lv = la + BACKWARD_MAX_ROWS;
+    const BackwardRec R = backward_rec(K, lds, want_g, want_a);
     const size_t step = (size_t)K.batch * (size_t)S, env = (size_t)b * (size_t)S;
     double cnt[2] = {0.0, 0.0}, sum[2] = {0.0, 0.0}, sq[2] = {0.0, 0.0};   // (indexed by constants only: registers)
     BackwardSampleIn<NR> cur, ahead;
@@ -230,25 +255,8 @@ PPG_DEVICE void backward_samples_env(const KP &K, unsigned char *lds, int b, int
         for (int q = 0; q < NR; ++q) {
             const int sp = q < NP ? 0 : 1;   // (a constant once the loop is unrolled)
             const uint32_t meta = cur.meta[q];
-            const int nx = (int)(int16_t)(uint16_t)meta;
-            const bool used = (meta & BACKWARD_META_USED) != 0;
-            const bool has = t + 1 < T && used && (meta & BACKWARD_META_STOP) == 0 && nx >= 0 && nx < S;
-            const int j = has ? nx : 0;   // the only LDS index a tensor's value ever becomes: checked against [0, S) above
-            double g_succ = 0.0, a_succ = 0.0, v_succ = 0.0;
-            if (t + 1 < T) {              // (wave-uniform; the arrays hold nothing yet at the last step)
-                if (want_g) { const double x = lg[j]; g_succ = has ? x : 0.0; }
-                if (want_a) { const double x = la[j], y = lv[j]; a_succ = has ? x : 0.0; v_succ = has ? y : 0.0; }
-            }
-            const double rew = cur.rew[q];
-            const double gm = g_succ * gamma;
-            const double gq = rew + gm;
-            g[q] = used ? gq : 0.0;
-            const double vm = v_succ * gamma;
-            const double boot = rew + vm;
-            const double delta = boot - cur.v[q];
-            const double am = a_succ * gl;
-            const double aq = delta + am;
-            a[q] = used ? aq : 0.0;
+            backward_row<S>(R, t + 1 < T, (meta & BACKWARD_META_USED) != 0, (meta & BACKWARD_META_STOP) != 0, (int16_t)(uint16_t)meta,
+                            cur.rew[q], cur.v[q], g[q], a[q]);
             const int32_t k = cur.k[q];
             if (k >= 0) {                 // stored: in use and 0 <= k < capacity[s] (backward_samples_load)
                 if (want_g) K.returns[sp][k] = (float)g[q];
@@ -262,14 +270,7 @@ PPG_DEVICE void backward_samples_env(const KP &K, unsigned char *lds, int b, int
             }
         }
         if (t == 0) break;
-        wv::sync();   // every lane has read step t + 1's values
-#pragma unroll
-        for (int q = 0; q < NR; ++q) {
-            const int r = 64 * q + ln;
-            if (want_g) lg[r] = g[q];
-            if (want_a) { la[r] = a[q]; lv[r] = cur.v[q]; }
-        }
-        wv::sync();   // step t's values are there for every lane
+        backward_publish(R, ln, g, a, cur.v);
         if (PREFETCH) cur = ahead;
     }
     if (STATS) {

@@ -118,6 +118,13 @@ static ppg_kernel_fn pick_kernel_p2(bool gen2, int nq, int mode) {
         if (e_ != hipSuccess) return ppg_fail(h, PPG_EHIP, "%s: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
+// make the handle's device the calling thread's current one
+static int backend_use_device(ppg_handle *h) {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
+    return PPG_OK;
+}
+
 static int backend_init(ppg_handle *h, int device) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return ppg_fail(h, PPG_ENODEV, "no HIP device visible");
@@ -137,8 +144,7 @@ static int backend_init(ppg_handle *h, int device) {
 }
 
 static int backend_alloc(ppg_handle *h, void **out, size_t bytes) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = backend_use_device(h)) return rc;
     PPG_HIP_TRY(h, hipMalloc(out, bytes));
     return PPG_OK;
 }
@@ -220,8 +226,7 @@ extern "C" __global__ void __launch_bounds__(1024) ppg_rank_envs(const int32_t *
 }
 
 static int backend_rebalance(ppg_handle *h, int weight_pred, int weight_prey, void *stream) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = backend_use_device(h)) return rc;
     if (!h->order_dev) PPG_HIP_TRY(h, hipMalloc((void **)&h->order_dev, (size_t)h->batch * sizeof(int32_t)));
     hipLaunchKernelGGL(ppg_rank_envs, dim3(1), dim3(1024), 0, (hipStream_t)stream,
                        (const int32_t *)h->bufs.env_state, (int)h->batch, weight_pred, weight_prey, h->order_dev,
@@ -231,133 +236,59 @@ static int backend_rebalance(ppg_handle *h, int weight_pred, int weight_prey, vo
     return PPG_OK;
 }
 
-// ---- ppg_pack: the packed observation image (ppg_pack.h) --------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(64) ppg_pack_scan(const ppg::PackParams K) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[512];
-    ppg::pack_scan_main(*PPG_KERNARG_PTR(ppg::PackParams, K), lds);
-}
-extern "C" __global__ void __launch_bounds__(64) ppg_pack_rows(const ppg::PackParams K) {
-    ppg::pack_rows_main(*PPG_KERNARG_PTR(ppg::PackParams, K));
+// ---- the learner-side kernels: one wavefront per workgroup, the parameter block by value ----------------------------------------
+// ppg_pack / ppg_fetch / ppg_link / ppg_record / ppg_record_obs / ppg_record_logp / ppg_backward / ppg_backward_samples (ppg_pack.h,
+// ppg_fetch.h, ppg_link.h, ppg_record.h, ppg_obs_store.h, ppg_logp.h, ppg_backward.h)
+#define PPG_ROWS_KERNEL(name, Params, main, lds_bytes)                                         \
+    extern "C" __global__ void __launch_bounds__(64) name(const ppg::Params K) {              \
+        __shared__ __attribute__((aligned(16))) unsigned char lds[lds_bytes];                  \
+        ppg::main(*PPG_KERNARG_PTR(ppg::Params, K), lds);                                      \
+    }
+#define PPG_ROWS_KERNEL_NO_LDS(name, Params, main)                                             \
+    extern "C" __global__ void __launch_bounds__(64) name(const ppg::Params K) { ppg::main(*PPG_KERNARG_PTR(ppg::Params, K)); }
+PPG_ROWS_KERNEL(ppg_pack_scan, PackParams, pack_scan_main, ppg::ROWS_SCAN_LDS_BYTES)
+PPG_ROWS_KERNEL_NO_LDS(ppg_pack_rows, PackParams, pack_rows_main)
+PPG_ROWS_KERNEL(ppg_fetch_rows, FetchParams, fetch_main, 1024)
+PPG_ROWS_KERNEL(ppg_link_rows, LinkParams, link_main, ppg::LINK_LDS_BYTES)
+PPG_ROWS_KERNEL(ppg_record_rows, RecordParams, record_main, ppg::LINK_LDS_BYTES)
+PPG_ROWS_KERNEL(ppg_obs_scan, ObsStoreParams, obs_scan_main, ppg::ROWS_SCAN_LDS_BYTES)
+PPG_ROWS_KERNEL_NO_LDS(ppg_obs_rows, ObsStoreParams, obs_rows_main)
+PPG_ROWS_KERNEL(ppg_logp_scan, LogpParams, logp_scan_main, ppg::ROWS_SCAN_LDS_BYTES)
+PPG_ROWS_KERNEL_NO_LDS(ppg_logp_rows, LogpParams, logp_rows_main)
+PPG_ROWS_KERNEL(ppg_backward_rows, BackwardParams, backward_main, ppg::BACKWARD_LDS_BYTES)
+PPG_ROWS_KERNEL(ppg_backward_samples_rows, BackwardSamplesParams, backward_samples_main, ppg::BACKWARD_LDS_BYTES)
+
+// `grid` one-wave workgroups of `kernel` on `stream`
+template <class Params>
+static int backend_launch_rows(ppg_handle *h, void (*kernel)(const Params), int grid, const Params &K, void *stream) {
+    if (int rc = backend_use_device(h)) return rc;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, K);
+    PPG_HIP_TRY(h, hipGetLastError());
+    return PPG_OK;
 }
 
 static int backend_pack(ppg_handle *h, const ppg::PackParams &K, void *stream) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(ppg_pack_scan, dim3(1), dim3(64), 0, (hipStream_t)stream, K);
-    hipLaunchKernelGGL(ppg_pack_rows, dim3((unsigned)K.n_envs), dim3(64), 0, (hipStream_t)stream, K);
-    PPG_HIP_TRY(h, hipGetLastError());
-    return PPG_OK;
+    if (int rc = backend_launch_rows(h, ppg_pack_scan, 1, K, stream)) return rc;
+    return backend_launch_rows(h, ppg_pack_rows, K.n_envs, K, stream);
 }
-
-// ---- ppg_fetch: the host view of a run of envs (ppg_fetch.h) ------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(64) ppg_fetch_rows(const ppg::FetchParams K) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[1024];
-    ppg::fetch_main(*PPG_KERNARG_PTR(ppg::FetchParams, K), lds);
-}
-
-static int backend_fetch(ppg_handle *h, const ppg::FetchParams &K, void *stream) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(ppg_fetch_rows, dim3((unsigned)K.n_envs), dim3(64), 0, (hipStream_t)stream, K);
-    PPG_HIP_TRY(h, hipGetLastError());
-    return PPG_OK;
-}
-
-// ---- ppg_link: rows of this call <-> rows of the previous link call (ppg_link.h) ----------------------------------
-extern "C" __global__ void __launch_bounds__(64) ppg_link_rows(const ppg::LinkParams K) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[ppg::LINK_LDS_BYTES];
-    ppg::link_main(*PPG_KERNARG_PTR(ppg::LinkParams, K), lds);
-}
-
-static int backend_link(ppg_handle *h, const ppg::LinkParams &K, void *stream) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(ppg_link_rows, dim3((unsigned)K.batch), dim3(64), 0, (hipStream_t)stream, K);
-    PPG_HIP_TRY(h, hipGetLastError());
-    return PPG_OK;
-}
-
-// ---- ppg_record: the link plus one step's stores into trajectory buffers (ppg_record.h) ----------------------------
-extern "C" __global__ void __launch_bounds__(64) ppg_record_rows(const ppg::RecordParams K) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[ppg::LINK_LDS_BYTES];
-    ppg::record_main(*PPG_KERNARG_PTR(ppg::RecordParams, K), lds);
-}
-
-static int backend_record(ppg_handle *h, const ppg::RecordParams &K, void *stream) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(ppg_record_rows, dim3((unsigned)K.batch), dim3(64), 0, (hipStream_t)stream, K);
-    PPG_HIP_TRY(h, hipGetLastError());
-    return PPG_OK;
-}
-
-// ---- ppg_record_obs: the rows in use appended to a per-species sample store (ppg_obs_store.h) ------------------------
-extern "C" __global__ void __launch_bounds__(64) ppg_obs_scan(const ppg::ObsStoreParams K) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[ppg::OBS_SCAN_LDS_BYTES];
-    ppg::obs_scan_main(*PPG_KERNARG_PTR(ppg::ObsStoreParams, K), lds);
-}
-extern "C" __global__ void __launch_bounds__(64) ppg_obs_rows(const ppg::ObsStoreParams K) {
-    ppg::obs_rows_main(*PPG_KERNARG_PTR(ppg::ObsStoreParams, K));
-}
-
+static int backend_fetch(ppg_handle *h, const ppg::FetchParams &K, void *stream) { return backend_launch_rows(h, ppg_fetch_rows, K.n_envs, K, stream); }
+static int backend_link(ppg_handle *h, const ppg::LinkParams &K, void *stream) { return backend_launch_rows(h, ppg_link_rows, K.batch, K, stream); }
+static int backend_record(ppg_handle *h, const ppg::RecordParams &K, void *stream) { return backend_launch_rows(h, ppg_record_rows, K.batch, K, stream); }
 static int backend_record_obs(ppg_handle *h, const ppg::ObsStoreParams &K, void *stream) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(ppg_obs_scan, dim3(1), dim3(64), 0, (hipStream_t)stream, K);
-    hipLaunchKernelGGL(ppg_obs_rows, dim3((unsigned)K.batch), dim3(64), 0, (hipStream_t)stream, K);
-    PPG_HIP_TRY(h, hipGetLastError());
-    return PPG_OK;
+    if (int rc = backend_launch_rows(h, ppg_obs_scan, 1, K, stream)) return rc;
+    return backend_launch_rows(h, ppg_obs_rows, K.batch, K, stream);
 }
-
-// ---- ppg_record_logp: the behaviour policy's log-probabilities into the sample store (ppg_logp.h) --------------------
-extern "C" __global__ void __launch_bounds__(64) ppg_logp_scan(const ppg::LogpParams K) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[ppg::LOGP_SCAN_LDS_BYTES];
-    ppg::logp_scan_main(*PPG_KERNARG_PTR(ppg::LogpParams, K), lds);
-}
-extern "C" __global__ void __launch_bounds__(64) ppg_logp_rows(const ppg::LogpParams K) {
-    ppg::logp_rows_main(*PPG_KERNARG_PTR(ppg::LogpParams, K));
-}
-
 static int backend_record_logp(ppg_handle *h, const ppg::LogpParams &K, void *stream) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(ppg_logp_scan, dim3(1), dim3(64), 0, (hipStream_t)stream, K);
-    hipLaunchKernelGGL(ppg_logp_rows, dim3((unsigned)K.batch), dim3(64), 0, (hipStream_t)stream, K);
-    PPG_HIP_TRY(h, hipGetLastError());
-    return PPG_OK;
+    if (int rc = backend_launch_rows(h, ppg_logp_scan, 1, K, stream)) return rc;
+    return backend_launch_rows(h, ppg_logp_rows, K.batch, K, stream);
 }
-
-// ---- ppg_backward: returns and GAE over a recorded horizon (ppg_backward.h) ---------------------------------------
-extern "C" __global__ void __launch_bounds__(64) ppg_backward_rows(const ppg::BackwardParams K) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[ppg::BACKWARD_LDS_BYTES];
-    ppg::backward_main(*PPG_KERNARG_PTR(ppg::BackwardParams, K), lds);
-}
-
-static int backend_backward(ppg_handle *h, const ppg::BackwardParams &K, void *stream) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(ppg_backward_rows, dim3((unsigned)K.batch), dim3(64), 0, (hipStream_t)stream, K);
-    PPG_HIP_TRY(h, hipGetLastError());
-    return PPG_OK;
-}
-
-// ---- ppg_backward_samples: the same recursion from and into sample order (ppg_backward.h) ------------------------------
-extern "C" __global__ void __launch_bounds__(64) ppg_backward_samples_rows(const ppg::BackwardSamplesParams K) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[ppg::BACKWARD_LDS_BYTES];
-    ppg::backward_samples_main(*PPG_KERNARG_PTR(ppg::BackwardSamplesParams, K), lds);
-}
-
+static int backend_backward(ppg_handle *h, const ppg::BackwardParams &K, void *stream) { return backend_launch_rows(h, ppg_backward_rows, K.batch, K, stream); }
 static int backend_backward_samples(ppg_handle *h, const ppg::BackwardSamplesParams &K, void *stream) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(ppg_backward_samples_rows, dim3((unsigned)K.batch), dim3(64), 0, (hipStream_t)stream, K);
-    PPG_HIP_TRY(h, hipGetLastError());
-    return PPG_OK;
+    return backend_launch_rows(h, ppg_backward_samples_rows, K.batch, K, stream);
 }
 
 static int backend_copy(ppg_handle *h, void *dst, const void *src, size_t bytes, bool to_device, void *stream) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = backend_use_device(h)) return rc;
     PPG_HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, (hipStream_t)stream));
     return PPG_OK;
 }
@@ -369,8 +300,7 @@ static int backend_sync(ppg_handle *h, void *stream) {
 
 static int backend_launch(ppg_handle *h, int mode, const ppg::KParams &P, void *stream) {
     // one workgroup = one wavefront = one environment
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) PPG_HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = backend_use_device(h)) return rc;
     const bool fast = P.nch_p <= 2 && P.nch_q <= 3;
     if (h->gen2 && mode > ppg::MODE_STEP_ORDERED && !(mode == ppg::MODE_VIS && h->cfg2.walls) &&
         !(mode == ppg::MODE_ROLLOUT && !h->cfg2.walls && P.coop_e > 0))

@@ -546,77 +546,98 @@ static int backend_pack(ppg_handle *h, const ppg::PackParams &K, void *stream);
 // the launch of ppg_fetch (ppg_fetch.h), and the release of a buffer from backend_alloc
 static int backend_fetch(ppg_handle *h, const ppg::FetchParams &K, void *stream);
 static void backend_free(ppg_handle *h, void *p);
-// the launch of ppg_link (ppg_link.h)
-#ifndef PPG_WAVE_EMU
+// the launches of ppg_link (ppg_link.h), ppg_record (ppg_record.h), ppg_record_obs (ppg_obs_store.h: two), ppg_record_logp
+// (ppg_logp.h: two), ppg_backward and ppg_backward_samples (ppg_backward.h)
 static int backend_link(ppg_handle *h, const ppg::LinkParams &K, void *stream);
-#else
-// CPU test build (tests/wave_emu): one single-wave workgroup per env, as on the device.  The test backend's files are frozen (a
-// feature change may only add test files), so this one launch is defined here instead of next to its backend_fetch.
-static void ppg_link_entry(void *arg) { ppg::link_main(*(const ppg::LinkParams *)arg, wv::emu().lds); }
-static int backend_link(ppg_handle *, const ppg::LinkParams &K, void *) {
-    for (int b = 0; b < K.batch; ++b) wv::run_block(ppg_link_entry, (void *)&K, b, ppg::LINK_LDS_BYTES, 1);
-    return PPG_OK;
-}
-#endif
-// the launch of ppg_record (ppg_record.h)
-#ifndef PPG_WAVE_EMU
 static int backend_record(ppg_handle *h, const ppg::RecordParams &K, void *stream);
-#else
-// (CPU test build: defined here for the same reason as backend_link)
-static void ppg_record_entry(void *arg) { ppg::record_main(*(const ppg::RecordParams *)arg, wv::emu().lds); }
-static int backend_record(ppg_handle *, const ppg::RecordParams &K, void *) {
-    for (int b = 0; b < K.batch; ++b) wv::run_block(ppg_record_entry, (void *)&K, b, ppg::LINK_LDS_BYTES, 1);
-    return PPG_OK;
-}
-#endif
-// the two launches of ppg_record_obs (ppg_obs_store.h)
-#ifndef PPG_WAVE_EMU
 static int backend_record_obs(ppg_handle *h, const ppg::ObsStoreParams &K, void *stream);
-#else
-// (CPU test build: defined here for the same reason as backend_link)
-static void ppg_obs_scan_entry(void *arg) { ppg::obs_scan_main(*(const ppg::ObsStoreParams *)arg, wv::emu().lds); }
-static void ppg_obs_rows_entry(void *arg) { ppg::obs_rows_main(*(const ppg::ObsStoreParams *)arg); }
-static int backend_record_obs(ppg_handle *, const ppg::ObsStoreParams &K, void *) {
-    wv::run_block(ppg_obs_scan_entry, (void *)&K, 0, ppg::OBS_SCAN_LDS_BYTES, 1);
-    for (int b = 0; b < K.batch; ++b) wv::run_block(ppg_obs_rows_entry, (void *)&K, b, 16, 1);
-    return PPG_OK;
-}
-#endif
-// the two launches of ppg_record_logp (ppg_logp.h)
-#ifndef PPG_WAVE_EMU
 static int backend_record_logp(ppg_handle *h, const ppg::LogpParams &K, void *stream);
-#else
-// (CPU test build: defined here for the same reason as backend_link)
-static void ppg_logp_scan_entry(void *arg) { ppg::logp_scan_main(*(const ppg::LogpParams *)arg, wv::emu().lds); }
-static void ppg_logp_rows_entry(void *arg) { ppg::logp_rows_main(*(const ppg::LogpParams *)arg); }
-static int backend_record_logp(ppg_handle *, const ppg::LogpParams &K, void *) {
-    wv::run_block(ppg_logp_scan_entry, (void *)&K, 0, ppg::LOGP_SCAN_LDS_BYTES, 1);
-    for (int b = 0; b < K.batch; ++b) wv::run_block(ppg_logp_rows_entry, (void *)&K, b, 16, 1);
-    return PPG_OK;
-}
-#endif
-// the launch of ppg_backward (ppg_backward.h)
-#ifndef PPG_WAVE_EMU
 static int backend_backward(ppg_handle *h, const ppg::BackwardParams &K, void *stream);
-#else
-// (CPU test build: defined here for the same reason as backend_link)
-static void ppg_backward_entry(void *arg) { ppg::backward_main(*(const ppg::BackwardParams *)arg, wv::emu().lds); }
-static int backend_backward(ppg_handle *, const ppg::BackwardParams &K, void *) {
-    for (int b = 0; b < K.batch; ++b) wv::run_block(ppg_backward_entry, (void *)&K, b, ppg::BACKWARD_LDS_BYTES, 1);
-    return PPG_OK;
-}
-#endif
-// the launch of ppg_backward_samples (ppg_backward.h)
-#ifndef PPG_WAVE_EMU
 static int backend_backward_samples(ppg_handle *h, const ppg::BackwardSamplesParams &K, void *stream);
-#else
-// (CPU test build: defined here for the same reason as backend_link)
-static void ppg_backward_samples_entry(void *arg) { ppg::backward_samples_main(*(const ppg::BackwardSamplesParams *)arg, wv::emu().lds); }
-static int backend_backward_samples(ppg_handle *, const ppg::BackwardSamplesParams &K, void *) {
-    for (int b = 0; b < K.batch; ++b) wv::run_block(ppg_backward_samples_entry, (void *)&K, b, ppg::BACKWARD_LDS_BYTES, 1);
+#ifdef PPG_WAVE_EMU
+// CPU test build (tests/wave_emu): `grid` one-wave workgroups of Main with exactly LDS bytes each, as on the device.  These six
+// launches stand here, not next to the test backend's backend_pack / backend_fetch: a revision's test suite is also run against
+// the sources of the revision after it, and its tests/wave_emu/ppg_emu.cpp defines only the launches that existed when it was written.
+template <class P, void (*Main)(const P &, unsigned char *), int LDS>
+static int ppg_emu_rows(const P &K, int grid) {
+    for (int b = 0; b < grid; ++b)
+        wv::run_block([](void *arg) { Main(*(const P *)arg, wv::emu().lds); }, (void *)&K, b, LDS, 1);
     return PPG_OK;
 }
+template <class P, void (*Main)(const P &)>   // (a main that takes no LDS)
+static int ppg_emu_rows(const P &K, int grid) {
+    for (int b = 0; b < grid; ++b) wv::run_block([](void *arg) { Main(*(const P *)arg); }, (void *)&K, b, 16, 1);
+    return PPG_OK;
+}
+static int backend_link(ppg_handle *, const ppg::LinkParams &K, void *) { return ppg_emu_rows<ppg::LinkParams, ppg::link_main, ppg::LINK_LDS_BYTES>(K, K.batch); }
+static int backend_record(ppg_handle *, const ppg::RecordParams &K, void *) {
+    return ppg_emu_rows<ppg::RecordParams, ppg::record_main, ppg::LINK_LDS_BYTES>(K, K.batch);
+}
+static int backend_record_obs(ppg_handle *, const ppg::ObsStoreParams &K, void *) {
+    ppg_emu_rows<ppg::ObsStoreParams, ppg::obs_scan_main, ppg::ROWS_SCAN_LDS_BYTES>(K, 1);
+    return ppg_emu_rows<ppg::ObsStoreParams, ppg::obs_rows_main>(K, K.batch);
+}
+static int backend_record_logp(ppg_handle *, const ppg::LogpParams &K, void *) {
+    ppg_emu_rows<ppg::LogpParams, ppg::logp_scan_main, ppg::ROWS_SCAN_LDS_BYTES>(K, 1);
+    return ppg_emu_rows<ppg::LogpParams, ppg::logp_rows_main>(K, K.batch);
+}
+static int backend_backward(ppg_handle *, const ppg::BackwardParams &K, void *) {
+    return ppg_emu_rows<ppg::BackwardParams, ppg::backward_main, ppg::BACKWARD_LDS_BYTES>(K, K.batch);
+}
+static int backend_backward_samples(ppg_handle *, const ppg::BackwardSamplesParams &K, void *) {
+    return ppg_emu_rows<ppg::BackwardSamplesParams, ppg::backward_samples_main, ppg::BACKWARD_LDS_BYTES>(K, K.batch);
+}
 #endif
+
+// ---- argument checks more than one call makes: `fn` is the calling function's name, each stands where the caller's own lines stood ----
+static int ppg_check_step_flags(ppg_handle *h, const int8_t *actions, uint32_t flags) {
+    if (!actions && !(flags & PPG_STEP_RANDOM_ACTIONS)) return ppg_fail(h, PPG_EINVAL, "actions is NULL without PPG_STEP_RANDOM_ACTIONS");
+    if (flags & ~(PPG_STEP_RANDOM_ACTIONS | PPG_STEP_AUTO_RESET)) return ppg_fail(h, PPG_EINVAL, "unknown step flags 0x%x", flags);
+    return PPG_OK;
+}
+
+static int ppg_check_horizon(ppg_handle *h, const char *fn, int32_t horizon) {
+    if (horizon < 1) return ppg_fail(h, PPG_EINVAL, "%s: horizon %d < 1", fn, horizon);
+    return PPG_OK;
+}
+
+// the step argument of a recording call (ppg_rows.h: RecordedStep): `step` is the index, or with the call's on-device flag (named
+// `flag`) the address of the device word
+template <int BIAS>
+static int ppg_step_arg(ppg_handle *h, const char *fn, const char *flag, bool on_device, uint64_t step, int32_t horizon,
+                        ppg::RecordedStep<BIAS> &at) {
+    if (on_device && !step) return ppg_fail(h, PPG_EINVAL, "%s: %s with a NULL address", fn, flag);
+    if (!on_device && step >= (uint64_t)horizon)
+        return ppg_fail(h, PPG_EINVAL, "%s: step %llu outside [0, %d)", fn, (unsigned long long)step, horizon);
+    at.T = horizon; at.step_on_device = on_device;
+    at.step = on_device ? 0 : (int32_t)step;
+    at.step_dev = on_device ? (const int32_t *)(uintptr_t)step : nullptr;
+    return PPG_OK;
+}
+
+// a sample store's capacities, and its slot table's int32 sample index
+static int ppg_check_store(ppg_handle *h, const char *fn, const ppg_obs_store *st) {
+    for (int s = 0; s < 2; ++s)
+        if (st->capacity[s] < 0 || st->capacity[s] > INT32_MAX)
+            return ppg_fail(h, PPG_EINVAL, "%s: capacity[%d] = %lld outside [0, 2^31)", fn, s, (long long)st->capacity[s]);
+    if ((uint64_t)st->horizon * (uint64_t)h->batch * (uint64_t)h->base.S > (uint64_t)INT32_MAX)
+        return ppg_fail(h, PPG_EINVAL, "%s: horizon %d x %d envs x %d rows does not fit the int32 sample index", fn, st->horizon, h->batch, h->base.S);
+    return PPG_OK;
+}
+
+static int ppg_check_backward_inputs(ppg_handle *h, const char *fn, const double *reward, const int16_t *next_row, const uint8_t *in_use,
+                                     const uint8_t *terminated, const uint8_t *truncated) {
+    if (!reward || !next_row || !in_use || !terminated || !truncated) return ppg_fail(h, PPG_EINVAL, "%s: an input pointer is NULL", fn);
+    return PPG_OK;
+}
+
+// the backward kernels' instantiations: 2 .. 6 row registers per lane
+static int ppg_check_backward_rows(ppg_handle *h, const char *fn) {
+    const int S = h->base.S;
+    if (S % 64 != 0 || S < 128 || S * 8 * 3 > ppg::BACKWARD_LDS_BYTES)
+        return ppg_fail(h, PPG_EINVAL, "%s: %d rows per env (needs a multiple of 64 in 128..%d)", fn, S, ppg::BACKWARD_MAX_ROWS);
+    return PPG_OK;
+}
 
 // The state tensors of one env, in image order (include/ppg.h: ppg_state_header): pointer, bytes per env.
 struct ppg_state_field { void *base; size_t bytes; };
@@ -828,8 +849,7 @@ static ppg::KParams ppg_planned_step_params(const ppg_handle *h, bool fused = fa
 
 int ppg_step(ppg_handle *h, const int8_t *actions, uint32_t flags, void *stream) {
     if (!h) return PPG_EINVAL;
-    if (!actions && !(flags & PPG_STEP_RANDOM_ACTIONS)) return ppg_fail(h, PPG_EINVAL, "actions is NULL without PPG_STEP_RANDOM_ACTIONS");
-    if (flags & ~(PPG_STEP_RANDOM_ACTIONS | PPG_STEP_AUTO_RESET)) return ppg_fail(h, PPG_EINVAL, "unknown step flags 0x%x", flags);
+    if (int rc = ppg_check_step_flags(h, actions, flags)) return rc;
     const int mode = h->cfg.kickback ? ppg::MODE_STEP_KICK : ppg::MODE_STEP;
     ppg::KParams P = ppg_planned_step_params(h);
     P.mode = mode; P.actions = actions; P.flags = flags; P.prof = h->prof_dev; P.n_steps = 1;
@@ -845,8 +865,7 @@ int ppg_rollout(ppg_handle *h, int32_t n_steps, const int8_t *actions, uint32_t 
     if (h->gen2 && (h->cfg2.walls || !(h->plan.coop_e > 0 && h->plan.nw == 4)))
         return ppg_fail(h, PPG_EINVAL, "ppg_rollout on a second-generation handle needs a cooperative four-wave plan (ppg_set_wave_plan) and no walls");
     if (h->drive) return ppg_fail(h, PPG_EINVAL, "ppg_rollout does not support the drive-conditioned variant");
-    if (!actions && !(flags & PPG_STEP_RANDOM_ACTIONS)) return ppg_fail(h, PPG_EINVAL, "actions is NULL without PPG_STEP_RANDOM_ACTIONS");
-    if (flags & ~(PPG_STEP_RANDOM_ACTIONS | PPG_STEP_AUTO_RESET)) return ppg_fail(h, PPG_EINVAL, "unknown step flags 0x%x", flags);
+    if (int rc = ppg_check_step_flags(h, actions, flags)) return rc;
     // a handle whose plan is cooperative with four-wave workgroups runs the fused form of that kernel; else one wave per env
     ppg::KParams P = (h->plan.coop_e > 0 && h->plan.nw == 4) ? ppg_planned_step_params(h, true) : h->base;
     P.mode = ppg::MODE_ROLLOUT; P.actions = actions; P.flags = flags; P.prof = h->prof_dev; P.n_steps = n_steps;
@@ -879,8 +898,7 @@ int ppg_step_uniforms(ppg_handle *h, const int8_t *actions, const uint8_t *act_r
     if (!h) return PPG_EINVAL;
     if (!h->gen2) return ppg_fail(h, PPG_EINVAL, "ppg_step_uniforms needs a handle from ppg_create_gen2");
     if (!uniforms || uniforms_per_env < 1) return ppg_fail(h, PPG_EINVAL, "uniforms is NULL or empty");
-    if (!actions && !(flags & PPG_STEP_RANDOM_ACTIONS)) return ppg_fail(h, PPG_EINVAL, "actions is NULL without PPG_STEP_RANDOM_ACTIONS");
-    if (flags & ~(PPG_STEP_RANDOM_ACTIONS | PPG_STEP_AUTO_RESET)) return ppg_fail(h, PPG_EINVAL, "unknown step flags 0x%x", flags);
+    if (int rc = ppg_check_step_flags(h, actions, flags)) return rc;
     if (act_rank && (flags & PPG_STEP_RANDOM_ACTIONS)) return ppg_fail(h, PPG_EINVAL, "act_rank with PPG_STEP_RANDOM_ACTIONS");
     ppg::KParams P = act_rank ? h->base : ppg_planned_step_params(h);   // (row order: the kernel the wave plan picks, like ppg_step)
     const int mode = act_rank ? ppg::MODE_STEP_ORDERED : ppg::MODE_STEP;
@@ -1274,22 +1292,17 @@ int ppg_record(ppg_handle *h, const ppg_record_buffers *buf, uint64_t step, uint
     if (!buf) return ppg_fail(h, PPG_EINVAL, "ppg_record: buf is NULL");
     if (!buf->reward || !buf->in_use || !buf->terminated || !buf->truncated || !buf->next_row)
         return ppg_fail(h, PPG_EINVAL, "ppg_record: a buffer of ppg_record_buffers is NULL");
-    if (buf->horizon < 1) return ppg_fail(h, PPG_EINVAL, "ppg_record: horizon %d < 1", buf->horizon);
+    if (int rc = ppg_check_horizon(h, "ppg_record", buf->horizon)) return rc;
     if (flags & ~PPG_RECORD_STEP_ON_DEVICE) return ppg_fail(h, PPG_EINVAL, "ppg_record: unknown flag bits 0x%x", flags);
-    const bool on_device = (flags & PPG_RECORD_STEP_ON_DEVICE) != 0;
-    if (on_device && !step) return ppg_fail(h, PPG_EINVAL, "ppg_record: PPG_RECORD_STEP_ON_DEVICE with a NULL address");
-    if (!on_device && step >= (uint64_t)buf->horizon)
-        return ppg_fail(h, PPG_EINVAL, "ppg_record: step %llu outside [0, %d)", (unsigned long long)step, buf->horizon);
+    ppg::RecordParams K;
+    memset((void *)&K, 0, sizeof K);
+    int rc = ppg_step_arg(h, "ppg_record", "PPG_RECORD_STEP_ON_DEVICE", (flags & PPG_RECORD_STEP_ON_DEVICE) != 0, step, buf->horizon, K);
+    if (rc != PPG_OK) return rc;
     const int S = h->base.S;
     if (S % 64 != 0 || S < 64 || S > ppg::LINK_MAX_ROWS)   // the kernel's row registers: S / 64 per lane
         return ppg_fail(h, PPG_EINVAL, "ppg_record: %d rows per env (needs a multiple of 64 up to %d)", S, ppg::LINK_MAX_ROWS);
-    ppg::RecordParams K;
-    memset((void *)&K, 0, sizeof K);
-    int rc = ppg_link_params(h, K, prev_row, next_row);
+    rc = ppg_link_params(h, K, prev_row, next_row);
     if (rc != PPG_OK) return rc;
-    K.T = buf->horizon; K.step_on_device = on_device;
-    K.step = on_device ? 0 : (int32_t)step;
-    K.step_dev = on_device ? (const int32_t *)(uintptr_t)step : nullptr;
     K.row_reward = (const uint64_t *)h->bufs.row_reward; K.reward = (uint64_t *)buf->reward;
     K.in_use = buf->in_use; K.terminated = buf->terminated; K.truncated = buf->truncated; K.traj_next = buf->next_row;
     rc = backend_record(h, K, stream);
@@ -1302,20 +1315,13 @@ int ppg_record_obs(ppg_handle *h, const ppg_obs_store *st, uint64_t step, uint32
     if (!st) return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: st is NULL");
     if (!st->slot || !st->cursor || !st->sample[0] || !st->sample[1] || !st->obs[0] || !st->obs[1])
         return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: slot, cursor, a sample[] or an obs[] of ppg_obs_store is NULL");
-    if (st->horizon < 1) return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: horizon %d < 1", st->horizon);
-    for (int s = 0; s < 2; ++s)
-        if (st->capacity[s] < 0 || st->capacity[s] > INT32_MAX)
-            return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: capacity[%d] = %lld outside [0, 2^31)", s, (long long)st->capacity[s]);
-    if ((uint64_t)st->horizon * (uint64_t)h->batch * (uint64_t)h->base.S > (uint64_t)INT32_MAX)
-        return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: horizon %d x %d envs x %d rows does not fit the int32 sample index", st->horizon, h->batch, h->base.S);
+    if (int rc = ppg_check_horizon(h, "ppg_record_obs", st->horizon)) return rc;
+    if (int rc = ppg_check_store(h, "ppg_record_obs", st)) return rc;
     if (!st->action[0] != !st->action[1]) return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: only one of the two action[] pointers is set");
     if (flags & ~(PPG_OBS_STEP_ON_DEVICE | PPG_OBS_F32)) return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: unknown flag bits 0x%x", flags);
-    const bool on_device = (flags & PPG_OBS_STEP_ON_DEVICE) != 0;
-    if (on_device && !step) return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: PPG_OBS_STEP_ON_DEVICE with a NULL address");
-    if (!on_device && step >= (uint64_t)st->horizon)
-        return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: step %llu outside [0, %d)", (unsigned long long)step, st->horizon);
     ppg::ObsStoreParams K;
-    memset(&K, 0, sizeof K);
+    memset((void *)&K, 0, sizeof K);   // ((void *): a block with a base -- RecordedStep -- is trivially copyable but not standard-layout)
+    if (int rc = ppg_step_arg(h, "ppg_record_obs", "PPG_OBS_STEP_ON_DEVICE", (flags & PPG_OBS_STEP_ON_DEVICE) != 0, step, st->horizon, K)) return rc;
     ppg_pack_geometry(h, (flags & PPG_OBS_F32) ? PPG_PACK_F32 : 0u, K.blk[0], K.blk[1], K.src_elem, K.dst_elem);
     if ((flags & PPG_OBS_F32) && K.src_elem < 4)
         return ppg_fail(h, PPG_EINVAL, "ppg_record_obs: PPG_OBS_F32 on a handle with %d-byte observation elements", K.src_elem);
@@ -1324,9 +1330,6 @@ int ppg_record_obs(ppg_handle *h, const ppg_obs_store *st, uint64_t step, uint32
         if (rc != PPG_OK) return rc;
     }
     K.batch = h->batch; K.S = h->base.S; K.cap_pred = h->base.cap_pred; K.cap_prey = h->base.cap_prey;
-    K.T = st->horizon; K.step_on_device = on_device;
-    K.step = on_device ? 0 : (int32_t)step;
-    K.step_dev = on_device ? (const int32_t *)(uintptr_t)step : nullptr;
     K.env_state = h->bufs.env_state;
     K.src[0] = (const unsigned char *)h->bufs.obs_pred; K.src[1] = (const unsigned char *)h->bufs.obs_prey;
     for (int s = 0; s < 2; ++s) {
@@ -1343,12 +1346,8 @@ int ppg_record_logp(ppg_handle *h, const ppg_obs_store *st, const ppg_logp_store
     if (!h) return PPG_EINVAL;
     if (!st || !out || !actions) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: st, out or actions is NULL");
     if (!st->slot) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: slot of ppg_obs_store is NULL");
-    if (st->horizon < 1) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: horizon %d < 1", st->horizon);
-    for (int s = 0; s < 2; ++s)
-        if (st->capacity[s] < 0 || st->capacity[s] > INT32_MAX)
-            return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: capacity[%d] = %lld outside [0, 2^31)", s, (long long)st->capacity[s]);
-    if ((uint64_t)st->horizon * (uint64_t)h->batch * (uint64_t)h->base.S > (uint64_t)INT32_MAX)
-        return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: horizon %d x %d envs x %d rows does not fit the int32 sample index", st->horizon, h->batch, h->base.S);
+    if (int rc = ppg_check_horizon(h, "ppg_record_logp", st->horizon)) return rc;
+    if (int rc = ppg_check_store(h, "ppg_record_logp", st)) return rc;
     const float *logits[2] = {logits_pred, logits_prey};
     for (int s = 0; s < 2; ++s) {
         if (!logits[s]) continue;
@@ -1359,21 +1358,15 @@ int ppg_record_logp(ppg_handle *h, const ppg_obs_store *st, const ppg_logp_store
     if (!out->entropy[0] != !out->entropy[1]) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: only one of the two entropy[] pointers is set");
     if (!out->dist[0] != !out->dist[1]) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: only one of the two dist[] pointers is set");
     if (flags & ~PPG_LOGP_STEP_ON_DEVICE) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: unknown flag bits 0x%x", flags);
-    const bool on_device = (flags & PPG_LOGP_STEP_ON_DEVICE) != 0;
-    if (on_device && !step) return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: PPG_LOGP_STEP_ON_DEVICE with a NULL address");
-    if (!on_device && step >= (uint64_t)st->horizon)
-        return ppg_fail(h, PPG_EINVAL, "ppg_record_logp: step %llu outside [0, %d)", (unsigned long long)step, st->horizon);
+    ppg::LogpParams K;
+    memset((void *)&K, 0, sizeof K);   // ((void *): as in ppg_record_obs)
+    if (int rc = ppg_step_arg(h, "ppg_record_logp", "PPG_LOGP_STEP_ON_DEVICE", (flags & PPG_LOGP_STEP_ON_DEVICE) != 0, step, st->horizon, K)) return rc;
     if (!logits[0] && !logits[1]) return PPG_OK;   // both species skipped
     if (!h->logp_off_dev) {
         const int rc = backend_alloc(h, (void **)&h->logp_off_dev, (size_t)h->batch * 2 * sizeof(int32_t));
         if (rc != PPG_OK) return rc;
     }
-    ppg::LogpParams K;
-    memset(&K, 0, sizeof K);
     K.batch = h->batch; K.S = h->base.S; K.cap_pred = h->base.cap_pred; K.cap_prey = h->base.cap_prey;
-    K.T = st->horizon; K.step_on_device = on_device;
-    K.step = on_device ? 0 : (int32_t)step;
-    K.step_dev = on_device ? (const int32_t *)(uintptr_t)step : nullptr;
     K.env_state = h->bufs.env_state;
     for (int s = 0; s < 2; ++s) {
         K.logits[s] = logits[s]; K.n_actions[s] = out->n_actions[s]; K.capacity[s] = st->capacity[s];
@@ -1388,17 +1381,15 @@ int ppg_backward(ppg_handle *h, int32_t n_steps, const double *reward, const int
                  double *returns, double *advantages, void *stream) {
     if (!h) return PPG_EINVAL;
     if (n_steps < 1) return ppg_fail(h, PPG_EINVAL, "ppg_backward: n_steps %d < 1", n_steps);
-    if (!reward || !next_row || !in_use || !terminated || !truncated) return ppg_fail(h, PPG_EINVAL, "ppg_backward: an input pointer is NULL");
+    if (int rc = ppg_check_backward_inputs(h, "ppg_backward", reward, next_row, in_use, terminated, truncated)) return rc;
     if (!returns && !advantages) return ppg_fail(h, PPG_EINVAL, "ppg_backward: returns and advantages are both NULL");
     if (advantages && !values) return ppg_fail(h, PPG_EINVAL, "ppg_backward: advantages need values");
     if (values && values_dtype != PPG_F64 && values_dtype != PPG_F32)
         return ppg_fail(h, PPG_EINVAL, "ppg_backward: values_dtype %d is neither PPG_F64 nor PPG_F32", values_dtype);
-    const int S = h->base.S;
-    if (S % 64 != 0 || S < 128 || S * 8 * 3 > ppg::BACKWARD_LDS_BYTES)   // the kernel's instantiations: 2 .. 6 row registers per lane
-        return ppg_fail(h, PPG_EINVAL, "ppg_backward: %d rows per env (needs a multiple of 64 in 128..%d)", S, ppg::BACKWARD_MAX_ROWS);
+    if (int rc = ppg_check_backward_rows(h, "ppg_backward")) return rc;
     ppg::BackwardParams K;
     memset(&K, 0, sizeof K);
-    K.batch = h->batch; K.S = S; K.T = n_steps;
+    K.batch = h->batch; K.S = h->base.S; K.T = n_steps;
     K.values_f32 = values && values_dtype == PPG_F32; K.prefetch = h->backward_prefetch;
     K.reward = reward; K.next_row = next_row; K.in_use = in_use; K.terminated = terminated; K.truncated = truncated;
     K.values = advantages ? values : nullptr;
@@ -1413,15 +1404,10 @@ int ppg_backward_samples(ppg_handle *h, int32_t n_steps, const double *reward, c
     if (!h) return PPG_EINVAL;
     if (!st || !tg) return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: st or tg is NULL");
     if (!st->slot) return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: slot of ppg_obs_store is NULL");
-    if (!reward || !next_row || !in_use || !terminated || !truncated)
-        return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: an input pointer is NULL");
+    if (int rc = ppg_check_backward_inputs(h, "ppg_backward_samples", reward, next_row, in_use, terminated, truncated)) return rc;
     if (n_steps < 1 || n_steps > st->horizon)
         return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: n_steps %d outside [1, horizon %d]", n_steps, st->horizon);
-    for (int s = 0; s < 2; ++s)
-        if (st->capacity[s] < 0 || st->capacity[s] > INT32_MAX)
-            return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: capacity[%d] = %lld outside [0, 2^31)", s, (long long)st->capacity[s]);
-    if ((uint64_t)st->horizon * (uint64_t)h->batch * (uint64_t)h->base.S > (uint64_t)INT32_MAX)
-        return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: horizon %d x %d envs x %d rows does not fit the int32 sample index", st->horizon, h->batch, h->base.S);
+    if (int rc = ppg_check_store(h, "ppg_backward_samples", st)) return rc;
     if (!tg->advantage[0] != !tg->advantage[1])
         return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: only one of the two advantage[] pointers is set");
     if (!tg->returns[0] != !tg->returns[1])
@@ -1430,12 +1416,10 @@ int ppg_backward_samples(ppg_handle *h, int32_t n_steps, const double *reward, c
     if (tg->stats && !tg->advantage[0]) return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: stats need advantage[]");
     if ((tg->values[0] || tg->values[1]) && values_dtype != PPG_F64 && values_dtype != PPG_F32)
         return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: values_dtype %d is neither PPG_F64 nor PPG_F32", values_dtype);
-    const int S = h->base.S;
-    if (S % 64 != 0 || S < 128 || S * 8 * 3 > ppg::BACKWARD_LDS_BYTES)   // the kernel's instantiations: 2 .. 6 row registers per lane
-        return ppg_fail(h, PPG_EINVAL, "ppg_backward_samples: %d rows per env (needs a multiple of 64 in 128..%d)", S, ppg::BACKWARD_MAX_ROWS);
+    if (int rc = ppg_check_backward_rows(h, "ppg_backward_samples")) return rc;
     ppg::BackwardSamplesParams K;
     memset(&K, 0, sizeof K);
-    K.batch = h->batch; K.S = S; K.T = n_steps; K.cap_pred = h->base.cap_pred;
+    K.batch = h->batch; K.S = h->base.S; K.T = n_steps; K.cap_pred = h->base.cap_pred;
     K.values_f32 = values_dtype == PPG_F32; K.prefetch = h->backward_samples_prefetch;
     K.reward = reward; K.next_row = next_row; K.in_use = in_use; K.terminated = terminated; K.truncated = truncated;
     K.slot = st->slot;

@@ -6,14 +6,14 @@
 // off_s[b] counts the rows of species s in use in the envs below b.  The slots slot[t][b][.] of the same rows are in the store
 // already (ppg_record_obs of step t), so two launches, both written against the wave primitives of wave.h (the CPU test build runs the
 // same source), put the two together:
-//   logp_scan  one wavefront: exclusive prefix sums of the two per-env row counts over B (the shape of obs_scan_main) -> a
+//   logp_scan  one wavefront: exclusive prefix sums of the two per-env row counts over B (rows_scan of ppg_rows.h) -> a
 //              library-owned [B,2] int32 scratch.
 //   logp_rows  one wavefront per env, one lane per row: the row's logits -> log-softmax at the action, entropy, a copy of the logits.
 // Arithmetic: float32 logits widened to float64, max-shifted, summed in ascending action order, rounded ONCE to float32 at the store;
 // no fused multiply-add (the library is built with -ffp-contract=off).  A logit of -inf is a masked action: its term is skipped,
 // never formed as 0 * inf.
-// Both kernels find the step index t the same way (a launch argument, or an int32 word in device memory that holds t + 1); with t
-// outside [0, T) neither writes anything.  A slot number becomes an address only after 0 <= k < capacity was checked, a logits row
+// Both kernels find the step index t the same way (ppg_rows.h: RecordedStep; the device word holds t + 1); with t outside [0, T)
+// neither writes anything.  A slot number becomes an address only after 0 <= k < capacity was checked, a logits row
 // only after 0 <= i < B * rows, an action indexes nothing at all.
 // Ordinary vector loads / stores and LDS accesses only.
 #pragma once
@@ -21,25 +21,14 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/ppg.h"
-
-#ifndef PPG_WAVE_EMU
-#include "wave.h"
-#endif
-
-#include "ppg_obs_store.h"
+#include "ppg_rows.h"
 
 namespace ppg {
 
-constexpr int LOGP_SCAN_LDS_BYTES = 64 * 2 * 4;
 constexpr uint32_t LOGP_QNAN_BITS = 0x7FC00000u;   // the quiet NaN a float32 tensor filled with NaN holds
 
-struct LogpParams {
+struct LogpParams : RecordedStep<1> {   // the device word holds t + 1; T = the horizon: slot is [T,B,S]
     int32_t batch, S, cap_pred, cap_prey;
-    int32_t T;                  // horizon: slot is [T,B,S]
-    int32_t step_on_device;     // t = *step_dev - 1 when the kernels run, else t = step
-    int32_t step;               // checked against [0, T) by the host
-    const int32_t *step_dev;
     const int32_t *env_state;
     const float *logits[2];     // [B * rows_s, n_actions[s]], the first sum_b n_s(b) rows written by ppg_policy_act; NULL: skipped
     int32_t n_actions[2];       // 1 .. 32
@@ -52,10 +41,6 @@ struct LogpParams {
     int32_t *off;               // library-owned [B,2]: logits row of the env's first row in use, per species
 };
 
-// the recorded step the logits belong to; int64 so that word - 1 cannot overflow (every lane reads the same word)
-template <class KP>
-PPG_DEVICE int64_t logp_step(const KP &K) { return K.step_on_device ? (int64_t)K.step_dev[0] - 1 : (int64_t)K.step; }
-
 PPG_DEVICE float logp_qnan() {
     union { uint32_t u; float f; } v;
     v.u = LOGP_QNAN_BITS;
@@ -65,33 +50,13 @@ PPG_DEVICE float logp_qnan() {
 // ---- launch 1: one wavefront ------------------------------------------------------------------------------------
 template <class KP>
 PPG_DEVICE void logp_scan_main(const KP &K, unsigned char *lds) {
-    const int ln = wv::lane();
-    uint32_t *tot = (uint32_t *)lds;  // [64][2]
-    const int per = (K.batch + 63) / 64;
-    const int lo = ln * per < K.batch ? ln * per : K.batch, hi = (lo + per) < K.batch ? (lo + per) : K.batch;
-    uint32_t sp = 0, sq = 0;
-    for (int e = lo; e < hi; ++e) {
-        const int32_t *es = K.env_state + (size_t)e * PPG_ENV_WORDS;
-        sp += (uint32_t)obs_rows_in_use(K, es, 0);
-        sq += (uint32_t)obs_rows_in_use(K, es, 1);
-    }
-    tot[2 * ln] = sp;
-    tot[2 * ln + 1] = sq;
-    wv::sync();
-    uint32_t bp = 0, bq = 0;
-    for (int l = 0; l < 64; ++l) {
-        const uint32_t a = tot[2 * l], b = tot[2 * l + 1];
-        if (l < ln) { bp += a; bq += b; }
-    }
-    const int64_t t = logp_step(K);
-    if (t < 0 || t >= K.T) return;   // (logp_rows checks t itself and then reads no offset)
-    for (int e = lo; e < hi; ++e) {
-        const int32_t *es = K.env_state + (size_t)e * PPG_ENV_WORDS;
+    auto count = [&](int e, int s) { return (uint32_t)rows_in_use(K, K.env_state + (size_t)e * PPG_ENV_WORDS, s); };
+    const RowScan r = rows_scan(K.batch, lds, count);
+    if (!step_in_horizon(K, recorded_step(K))) return;   // (logp_rows checks t itself and then reads no offset)
+    rows_scan_each(r, count, [&](int e, uint32_t bp, uint32_t bq) {
         K.off[2 * e] = (int32_t)bp;   // (at most B * rows per species, which the host holds below 2^31)
         K.off[2 * e + 1] = (int32_t)bq;
-        bp += (uint32_t)obs_rows_in_use(K, es, 0);
-        bq += (uint32_t)obs_rows_in_use(K, es, 1);
-    }
+    });
 }
 
 // One row of A float32 logits: log-softmax at action a (quiet NaN for an action outside [0, A)) and the entropy, in float64, each
@@ -127,14 +92,14 @@ PPG_DEVICE void logp_rows_main(const KP &K) {
     const int b = PPG_BLOCK_INDEX();
     if (b >= K.batch) return;
     const int ln = wv::lane();
-    const int64_t t = logp_step(K);
-    if (t < 0 || t >= K.T) return;   // nothing recorded yet, or a replay past the horizon.  The ONLY uses of t as an index come after this check
+    const int64_t t = recorded_step(K);
+    if (!step_in_horizon(K, t)) return;   // nothing recorded yet, or a replay past the horizon
     const int S = K.S;
     const int32_t *es = K.env_state + (size_t)b * PPG_ENV_WORDS;
     const size_t at = ((size_t)t * K.batch + (size_t)b) * S;
     // The env's predator rows and then its prey rows share ONE run of lanes (a species without logits has no rows here): at the
     // default population an env has 6 + 7 rows in use, and a lane costs the same whether 6 or 13 of its neighbours work.
-    const int n0 = K.logits[0] ? obs_rows_in_use(K, es, 0) : 0, n1 = K.logits[1] ? obs_rows_in_use(K, es, 1) : 0;
+    const int n0 = K.logits[0] ? rows_in_use(K, es, 0) : 0, n1 = K.logits[1] ? rows_in_use(K, es, 1) : 0;
     for (int q = ln; q < n0 + n1; q += 64) {
         const bool s = q >= n0;
         const int j = s ? q - n0 : q, first = s ? K.cap_pred : 0, cap = s ? K.cap_prey : K.cap_pred;

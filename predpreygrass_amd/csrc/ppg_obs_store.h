@@ -2,37 +2,27 @@
 // per-species sample store on the device, with the (t, b, r) each slot holds and the action taken from it one call later.
 //
 // Two launches, both written against the wave primitives of wave.h (the CPU test build runs the same source):
-//   obs_scan  one wavefront: exclusive prefix sums of the two per-env row counts over B (the shape of pack_scan_main), plus the cursor
+//   obs_scan  one wavefront: exclusive prefix sums of the two per-env row counts over B (rows_scan of ppg_rows.h), plus the cursor
 //             -> absolute per-env slot bases in a library-owned [B,2] int64 scratch, then the four cursor words.  The only writer of
 //             the cursor: no atomics.
 //   obs_rows  one wavefront per env: slot[t] of its S rows, the sample words and PPG_ACTION_UNSET of the rows it stores, the actions
 //             of step t - 1 through slot[t-1], and the observation copies.
 // The rows in use of an env are the FIRST n rows of its region of the observation tensor, and their slots are consecutive, so an
 // env's observations are two contiguous copies (predators, prey), each cut where the store's capacity ends.
-// Both kernels request the step index t the same way (a launch argument, or an int32 word in device memory); with t outside [0, T)
-// neither writes anything.  A slot number becomes an address only after 0 <= k < capacity was checked -- the bases come from the
+// Both kernels request the step index t the same way (ppg_rows.h: RecordedStep); with t outside [0, T) neither writes anything.
+// A slot number becomes an address only after 0 <= k < capacity was checked -- the bases come from the
 // scratch, slot[t-1] from the caller: both are device memory.
 // Ordinary vector loads / stores and LDS accesses only.
 #pragma once
 
 #include <stdint.h>
 
-#include "../../include/ppg.h"
-
-#ifndef PPG_WAVE_EMU
-#include "wave.h"
-#endif
+#include "ppg_rows.h"
 
 namespace ppg {
 
-constexpr int OBS_SCAN_LDS_BYTES = 64 * 2 * 4;
-
-struct ObsStoreParams {
+struct ObsStoreParams : RecordedStep<0> {   // the device word holds t; T = the horizon: slot is [T,B,S]
     int32_t batch, S, cap_pred, cap_prey;
-    int32_t T;                  // horizon: slot is [T,B,S]
-    int32_t step_on_device;     // t = *step_dev when the kernels run, else t = step
-    int32_t step;               // checked against [0, T) by the host
-    const int32_t *step_dev;
     const int32_t *env_state;
     const unsigned char *src[2];   // obs_pred / obs_prey of the handle
     int32_t blk[2];                // elements per observation block
@@ -53,59 +43,28 @@ struct alignas(16) ObsStore16 { uint32_t a, b, c, d; };
 struct __attribute__((packed, aligned(8))) ObsLoadD2 { double x, y; };
 struct alignas(16) ObsStoreF4 { float x, y, z, w; };
 
-template <class KP>
-PPG_DEVICE int obs_step(const KP &K) { return K.step_on_device ? K.step_dev[0] : K.step; }   // (every lane reads the same word)
-
-// rows in use of species s in an env, as ppg_record's in_use sees them: never more than the region holds
-template <class KP>
-PPG_DEVICE int obs_rows_in_use(const KP &K, const int32_t *es, int s) {
-    const int n = es[s ? PPG_ENV_N_PREY_ROWS : PPG_ENV_N_PRED_ROWS], cap = s ? K.cap_prey : K.cap_pred;
-    return n < 0 ? 0 : n > cap ? cap : n;
-}
-
 // ---- launch 1: one wavefront ------------------------------------------------------------------------------------
 template <class KP>
 PPG_DEVICE void obs_scan_main(const KP &K, unsigned char *lds) {
     const int ln = wv::lane();
-    uint32_t *tot = (uint32_t *)lds;  // [64][2]
-    const int t = obs_step(K);
-    const bool live = t >= 0 && t < K.T;
-    const int per = (K.batch + 63) / 64;
-    const int lo = ln * per < K.batch ? ln * per : K.batch, hi = (lo + per) < K.batch ? (lo + per) : K.batch;
+    const bool live = step_in_horizon(K, recorded_step(K));
     int64_t cur[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {   // the cursor as a slot number: inside [0, capacity] whatever the word holds
         const int64_t c = K.cursor[s];
         cur[s] = c < 0 ? 0 : c > K.capacity[s] ? K.capacity[s] : c;
     }
-    uint32_t sp = 0, sq = 0;
-    for (int e = lo; e < hi; ++e) {
-        const int32_t *es = K.env_state + (size_t)e * PPG_ENV_WORDS;
-        sp += (uint32_t)obs_rows_in_use(K, es, 0);
-        sq += (uint32_t)obs_rows_in_use(K, es, 1);
-    }
-    tot[2 * ln] = sp;
-    tot[2 * ln + 1] = sq;
-    wv::sync();
-    uint32_t bp = 0, bq = 0, tp = 0, tq = 0;
-    for (int l = 0; l < 64; ++l) {
-        const uint32_t a = tot[2 * l], b = tot[2 * l + 1];
-        if (l < ln) { bp += a; bq += b; }
-        tp += a; tq += b;
-    }
-    for (int e = lo; e < hi; ++e) {
-        const int32_t *es = K.env_state + (size_t)e * PPG_ENV_WORDS;
+    auto count = [&](int e, int s) { return (uint32_t)rows_in_use(K, K.env_state + (size_t)e * PPG_ENV_WORDS, s); };
+    const RowScan r = rows_scan(K.batch, lds, count);
+    rows_scan_each(r, count, [&](int e, uint32_t bp, uint32_t bq) {
         // a step index outside [0, T): bases at the capacity, with which obs_rows (which checks t itself) could store no row
         K.base[2 * e] = live ? cur[0] + (int64_t)bp : K.capacity[0];
         K.base[2 * e + 1] = live ? cur[1] + (int64_t)bq : K.capacity[1];
-        bp += (uint32_t)obs_rows_in_use(K, es, 0);
-        bq += (uint32_t)obs_rows_in_use(K, es, 1);
-    }
+    });
     if (ln == 0 && live) {
-        const int64_t total[2] = {(int64_t)tp, (int64_t)tq};
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const int64_t end = cur[s] + total[s], kept = end < K.capacity[s] ? end : K.capacity[s];
+            const int64_t end = cur[s] + (int64_t)r.total[s], kept = end < K.capacity[s] ? end : K.capacity[s];
             const int64_t dropped = K.cursor[2 + s];
             K.cursor[s] = kept;
             K.cursor[2 + s] = dropped + (end - kept);
@@ -175,8 +134,8 @@ PPG_DEVICE void obs_rows_main(const KP &K) {
     const int b = PPG_BLOCK_INDEX();
     if (b >= K.batch) return;
     const int ln = wv::lane();
-    const int t = obs_step(K);
-    if (t < 0 || t >= K.T) return;   // a replay past the horizon: nothing.  The ONLY uses of t as an index come after this check
+    const int64_t t = recorded_step(K);
+    if (!step_in_horizon(K, t)) return;   // a replay past the horizon: nothing
     const int S = K.S;
     const int32_t *es = K.env_state + (size_t)b * PPG_ENV_WORDS;
     const size_t step = (size_t)K.batch * S, at = (size_t)t * step + (size_t)b * S;
@@ -184,7 +143,7 @@ PPG_DEVICE void obs_rows_main(const KP &K) {
 #pragma unroll
     for (int s = 0; s < 2; ++s) {   // predators, then prey: rows [first, first + cap) of the env
         const int first = s ? K.cap_pred : 0, cap = s ? K.cap_prey : K.cap_pred;
-        const int n = obs_rows_in_use(K, es, s);
+        const int n = rows_in_use(K, es, s);
         const int64_t base = K.base[2 * b + s], capacity = K.capacity[s];
         int32_t *sample = K.sample[s];
         int8_t *action = K.action[s];

@@ -3,7 +3,7 @@
 // (the reference has no counterpart: its dicts live in one Python process, BASE:456-473).
 //
 // Two launches, both written against the wave primitives of wave.h (the CPU test build runs the same source):
-//   pack_scan  one wavefront: exclusive prefix sums of the per-env row counts -> row_off section + header
+//   pack_scan  one wavefront: exclusive prefix sums of the per-env row counts (rows_scan of ppg_rows.h) -> row_off section + header
 //   pack_rows  one wavefront per env: env words, the per-row scalars and the observation blocks of the rows in use.
 // The rows in use of an env are the FIRST n rows of its region of every table, so an env's observations are two
 // contiguous copies (predators, prey): 16 bytes per lane when the block size allows it, float64 -> float32 on request.
@@ -11,11 +11,7 @@
 
 #include <stdint.h>
 
-#include "../../include/ppg.h"
-
-#ifndef PPG_WAVE_EMU
-#include "wave.h"
-#endif
+#include "ppg_rows.h"
 
 namespace ppg {
 
@@ -75,35 +71,19 @@ PPG_DEVICE int pack_handle_of(const KP &K, int e) {
 template <class KP>
 PPG_DEVICE void pack_scan_main(const KP &K, unsigned char *lds) {
     const int ln = wv::lane();
-    uint32_t *tot = (uint32_t *)lds;  // [64][2]
-    const int per = (K.n_envs + 63) / 64;
-    const int lo = ln * per, hi = (lo + per) < K.n_envs ? (lo + per) : K.n_envs;
-    uint32_t sp = 0, sq = 0;
-    for (int e = lo; e < hi; ++e) {
+    // the env words as they are, NOT clamped to the region: the header and the offsets describe what pack_rows copies
+    auto count = [&](int e, int s) {
         const int k = pack_handle_of(K, e);
-        const int32_t *es = K.env_state[k] + (size_t)(e - K.env_base[k]) * PPG_ENV_WORDS;
-        sp += (uint32_t)es[PPG_ENV_N_PRED_ROWS];
-        sq += (uint32_t)es[PPG_ENV_N_PREY_ROWS];
-    }
-    tot[2 * ln] = sp;
-    tot[2 * ln + 1] = sq;
-    wv::sync();
-    uint32_t bp = 0, bq = 0, tp = 0, tq = 0;
-    for (int l = 0; l < 64; ++l) {
-        const uint32_t a = tot[2 * l], b = tot[2 * l + 1];
-        if (l < ln) { bp += a; bq += b; }
-        tp += a; tq += b;
-    }
+        return (uint32_t)K.env_state[k][(size_t)(e - K.env_base[k]) * PPG_ENV_WORDS + (s ? PPG_ENV_N_PREY_ROWS : PPG_ENV_N_PRED_ROWS)];
+    };
+    const RowScan r = rows_scan(K.n_envs, lds, count);
+    const uint32_t tp = r.total[0], tq = r.total[1];
     const PackLayout L = pack_layout((uint64_t)K.n_envs, tp, tq, (uint64_t)K.blk_pred, (uint64_t)K.blk_prey, (uint64_t)K.dst_elem);
     uint32_t *row_off = (uint32_t *)(K.out + L.row_off);
-    for (int e = lo; e < hi; ++e) {
-        const int k = pack_handle_of(K, e);
-        const int32_t *es = K.env_state[k] + (size_t)(e - K.env_base[k]) * PPG_ENV_WORDS;
+    rows_scan_each(r, count, [&](int e, uint32_t bp, uint32_t bq) {
         row_off[2 * e] = bp;
         row_off[2 * e + 1] = bq;
-        bp += (uint32_t)es[PPG_ENV_N_PRED_ROWS];
-        bq += (uint32_t)es[PPG_ENV_N_PREY_ROWS];
-    }
+    });
     if (ln == 0) {
         ppg_pack_header *H = (ppg_pack_header *)K.out;
         H->magic = PPG_PACK_MAGIC; H->version = PPG_PACK_VERSION;

@@ -2,11 +2,10 @@
 // predpreygrass_amd.trajectory.AgentTrajectories keeps one env step, in ONE launch (as torch ops behind ppg_link: about nineteen).
 //
 // One wavefront per env, written against the wave primitives of wave.h (the CPU test build runs the same source).  The wavefront
-//   1. requests the step index t: a launch argument, or (step_on_device) an int32 word in device memory read when the kernel runs,
-//      so that a hipGraph holding step + record can be replayed while another node of the graph counts the word up;
+//   1. requests the step index t (ppg_rows.h: RecordedStep);
 //   2. links its env (link_env of ppg_link.h: the same code, snapshot and outputs as ppg_link_rows), after which next[] of both
 //      species is still in LDS;
-//   3. if 0 <= t < T -- the ONLY use of t as an index comes after this check -- writes for its rows r = 64q + lane
+//   3. if 0 <= t < T writes for its rows r = 64q + lane
 //        next_row[t-1][b][r] = next[r] from LDS (only if t > 0)      next_row[t][b][r] = -1
 //        reward[t][b][r]     = the bits of row_reward[b][r] (all S rows: what a copy of the tensor does)
 //        in_use[t][b][r]     = r < cap_pred ? r < n_pred_rows : r - cap_pred < n_prey_rows
@@ -18,16 +17,13 @@
 #include <stdint.h>
 
 #include "ppg_link.h"
+#include "ppg_rows.h"
 
 namespace ppg {
 
 constexpr int RECORD_MAX_REGS = LINK_MAX_ROWS / 64;   // row registers per lane at the largest S
 
-struct RecordParams : LinkParams {
-    int32_t T;                  // horizon: the buffers are [T,B,S]
-    int32_t step_on_device;     // t = *step_dev when the kernel runs, else t = step
-    int32_t step;               // checked against [0, T) by the host
-    const int32_t *step_dev;
+struct RecordParams : LinkParams, RecordedStep<0> {   // the device word holds t; T = the horizon: the buffers are [T,B,S]
     const uint64_t *row_reward; // [B,S] float64, moved as bits
     uint64_t *reward;           // [T,B,S]
     uint8_t *in_use, *terminated, *truncated;   // [T,B,S], 0 / 1
@@ -42,7 +38,7 @@ PPG_DEVICE void record_main(const KP &K, unsigned char *lds) {
     const int S = K.S;   // a multiple of 64, at most LINK_MAX_ROWS (the host refuses anything else): row registers q < S / 64 <= 6
     const size_t row0 = (size_t)b * S;
     // what the stores need and the link does not depend on is requested first: the loads return while the link runs
-    const int t = K.step_on_device ? K.step_dev[0] : K.step;   // (every lane reads the same word)
+    const int64_t t = recorded_step(K);
     uint8_t f[RECORD_MAX_REGS];
     uint64_t rew[RECORD_MAX_REGS];
 #pragma unroll
@@ -52,7 +48,7 @@ PPG_DEVICE void record_main(const KP &K, unsigned char *lds) {
         rew[q] = r < S ? K.row_reward[row0 + r] : (uint64_t)0;
     }
     const LinkRows n = link_env(K, lds, b, ln);
-    if (t < 0 || t >= K.T) return;   // a replay past the horizon: the link above, and nothing else
+    if (!step_in_horizon(K, t)) return;   // a replay past the horizon: the link above, and nothing else
     wv::sync();
     const int16_t *nxt = (const int16_t *)(lds + (size_t)LINK_MAX_ROWS * 4);
     const size_t step = (size_t)K.batch * S, at = (size_t)t * step + row0;

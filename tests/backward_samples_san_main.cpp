@@ -5,37 +5,11 @@
 // slots, [capacity[s]] values and outputs, [B,2,3] stats -- so a slot word that escaped its range check, or any other access outside
 // a tensor, traps.  The outputs are compared bit for bit with a scalar recursion written from the formulas of include/ppg.h.
 // Exit status 0 = clean and equal.
-#include "wave_emu/wave_emu.h"
-
-#include <math.h>
-
-#include <vector>
+#include "wave_emu/san_main.h"
 
 #include "../predpreygrass_amd/csrc/ppg_backward.h"
 
-#if defined(__x86_64__)
-__asm__(
-    ".text\n"
-    ".globl ppg_emu_ctx_switch\n"
-    ".type ppg_emu_ctx_switch,@function\n"
-    "ppg_emu_ctx_switch:\n"
-    "  pushq %rbp\n  pushq %rbx\n  pushq %r12\n  pushq %r13\n  pushq %r14\n  pushq %r15\n"
-    "  movq %rsp, (%rdi)\n"
-    "  movq %rsi, %rsp\n"
-    "  popq %r15\n  popq %r14\n  popq %r13\n  popq %r12\n  popq %rbx\n  popq %rbp\n"
-    "  ret\n"
-    ".size ppg_emu_ctx_switch, .-ppg_emu_ctx_switch\n");
-#else
-#error "wave emulator context switch is written for x86-64"
-#endif
-
-static uint64_t g_lcg = 0x2545F4914F6CDD1Dull;
-static uint32_t rnd() {
-    g_lcg = g_lcg * 6364136223846793005ull + 1442695040888963407ull;
-    return (uint32_t)(g_lcg >> 33);
-}
-static int below(int n) { return (int)(rnd() % (uint32_t)n); }
-static double unit() { return (double)rnd() / 2147483648.0; }
+constexpr uint64_t SEED = 0x2545F4914F6CDD1Dull;
 
 struct Case {
     int T, H, B, S, cp;          // H: the store's horizon (T + 1: one step of slots the call must not read)
@@ -174,7 +148,6 @@ static void reference(const Case &c, bool f32, bool no_pred_values, double gamma
     }
 }
 
-static void entry(void *arg) { ppg::backward_samples_main(*(const ppg::BackwardSamplesParams *)arg, wv::emu().lds); }
 
 static bool differ(const std::vector<float> &a, const std::vector<float> &b) {
     return a.size() != b.size() || (a.size() && memcmp(a.data(), b.data(), a.size() * 4) != 0);
@@ -204,7 +177,7 @@ static int run(const Case &c, bool want_g, bool want_a, bool want_stats, bool f3
     }
     K.gamma = gamma; K.gl = gamma * lam;
     K.stats = want_stats ? got.stats.data() : nullptr;
-    for (int b = 0; b < c.B; ++b) wv::run_block(entry, &K, b, ppg::BACKWARD_LDS_BYTES, 1);
+    run_grid<ppg::BackwardSamplesParams, ppg::backward_samples_main, ppg::BACKWARD_LDS_BYTES>(K, c.B);
     reference(c, f32, no_pred_values, gamma, lam, want);
     int bad = 0;
     for (int s = 0; s < 2; ++s) {
@@ -218,6 +191,7 @@ static int run(const Case &c, bool want_g, bool want_a, bool want_stats, bool f3
 }
 
 int main() {
+    lcg_seed(SEED);
     int bad = 0;
     char tag[128];
     static const int shapes[3][2] = {{64, 64}, {64, 128}, {128, 256}};

@@ -3,37 +3,11 @@
 // exactly the LDS the HIP launch declares (ppg::BACKWARD_LDS_BYTES); the emulator poisons the bytes behind it, and the tensors are
 // heap blocks of exactly [T,B,S] elements, so an access outside either traps.  The outputs are compared bit for bit with a scalar
 // recursion written from the formulas of include/ppg.h.  Exit status 0 = clean and equal.
-#include "wave_emu/wave_emu.h"
-
-#include <math.h>
-
-#include <vector>
+#include "wave_emu/san_main.h"
 
 #include "../predpreygrass_amd/csrc/ppg_backward.h"
 
-#if defined(__x86_64__)
-__asm__(
-    ".text\n"
-    ".globl ppg_emu_ctx_switch\n"
-    ".type ppg_emu_ctx_switch,@function\n"
-    "ppg_emu_ctx_switch:\n"
-    "  pushq %rbp\n  pushq %rbx\n  pushq %r12\n  pushq %r13\n  pushq %r14\n  pushq %r15\n"
-    "  movq %rsp, (%rdi)\n"
-    "  movq %rsi, %rsp\n"
-    "  popq %r15\n  popq %r14\n  popq %r13\n  popq %r12\n  popq %rbx\n  popq %rbp\n"
-    "  ret\n"
-    ".size ppg_emu_ctx_switch, .-ppg_emu_ctx_switch\n");
-#else
-#error "wave emulator context switch is written for x86-64"
-#endif
-
-static uint64_t g_lcg = 0x2545F4914F6CDD1Dull;
-static uint32_t rnd() {
-    g_lcg = g_lcg * 6364136223846793005ull + 1442695040888963407ull;
-    return (uint32_t)(g_lcg >> 33);
-}
-static int below(int n) { return (int)(rnd() % (uint32_t)n); }
-static double unit() { return (double)rnd() / 2147483648.0; }
+constexpr uint64_t SEED = 0x2545F4914F6CDD1Dull;
 
 struct Case {
     int T, B, S;
@@ -103,7 +77,6 @@ static void reference(const Case &c, bool f32, double gamma, double lam, std::ve
             }
 }
 
-static void entry(void *arg) { ppg::backward_main(*(const ppg::BackwardParams *)arg, wv::emu().lds); }
 
 static int run(const Case &c, bool want_g, bool want_a, bool f32, int prefetch, const char *tag) {
     const double gamma = 0.97, lam = 0.9;
@@ -117,7 +90,7 @@ static int run(const Case &c, bool want_g, bool want_a, bool f32, int prefetch, 
     K.values = !want_a ? nullptr : f32 ? (const void *)c.values32.data() : (const void *)c.values.data();
     K.gamma = gamma; K.gl = gamma * lam;
     K.returns = want_g ? G.data() : nullptr; K.advantages = want_a ? A.data() : nullptr;
-    for (int b = 0; b < c.B; ++b) wv::run_block(entry, &K, b, ppg::BACKWARD_LDS_BYTES, 1);
+    run_grid<ppg::BackwardParams, ppg::backward_main, ppg::BACKWARD_LDS_BYTES>(K, c.B);
     reference(c, f32, gamma, lam, wantG, wantA);
     int bad = 0;
     if (want_g && memcmp(G.data(), wantG.data(), n * 8) != 0) { fprintf(stderr, "%s: returns differ\n", tag); bad = 1; }
@@ -128,6 +101,7 @@ static int run(const Case &c, bool want_g, bool want_a, bool f32, int prefetch, 
 }
 
 int main() {
+    lcg_seed(SEED);
     int bad = 0;
     char tag[96];
     for (int S : {128, 384})

@@ -4,21 +4,33 @@ so the device code and the host wrappers can be exercised on a machine without a
 The product package never imports this."""
 import ctypes
 import os
+import re
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU_DIR = os.path.join(ROOT, "tests", "wave_emu")
 EMU_LIB = os.path.join(EMU_DIR, "libppg_emu.so")
-_KERNEL_SOURCES = [
-    os.path.join(EMU_DIR, "ppg_emu_part.cpp"), os.path.join(EMU_DIR, "wave_emu.h"),
-    os.path.join(ROOT, "predpreygrass_amd", "csrc", "ppg_kernel.h"),
-    *[os.path.join(ROOT, "predpreygrass_amd", "csrc", f"ppg_env_{p}.h")   # struct Env's member functions, one file per phase
-      for p in ("load", "move", "sort", "observe", "coop", "engage", "reproduce", "step")],
-    os.path.join(ROOT, "include", "ppg.h"),
-]
-_SOURCES = _KERNEL_SOURCES + [os.path.join(EMU_DIR, "ppg_emu.cpp"), os.path.join(ROOT, "predpreygrass_amd", "csrc", "ppg_host.h"),
-                              os.path.join(ROOT, "predpreygrass_amd", "csrc", "ppg_pack.h"),
-                              os.path.join(ROOT, "predpreygrass_amd", "csrc", "ppg_fetch.h")]
+_UNITS = ("ppg_emu.cpp", "ppg_emu_part.cpp")   # the dispatch / C-ABI unit and the kernel unit (compiled twelve times)
+_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
+
+
+def include_closure(path, seen=None):
+    """`path` and every file it reaches through #include "..." lines, transitively (conditional includes count: a superset)."""
+    seen = set() if seen is None else seen
+    path = os.path.normpath(path)
+    if path not in seen:
+        seen.add(path)
+        with open(path) as f:
+            for inc in _INCLUDE.findall(f.read()):
+                include_closure(os.path.join(os.path.dirname(path), inc), seen)
+    return seen
+
+
+def sources():
+    """The files build() checks for staleness: everything the two units include, so no header can be forgotten."""
+    return sorted(set().union(*(include_closure(os.path.join(EMU_DIR, u)) for u in _UNITS)))
+
+
 _lib = None
 
 
@@ -38,7 +50,7 @@ def build(sanitize=False):
     LDS READ traps too (round 3's advisor found one that UBSan cannot see)."""
     asan = sanitize == "address"
     out = EMU_LIB if not sanitize else EMU_LIB.replace(".so", "_asan.so" if asan else "_ubsan.so")
-    if not _stale(out, _SOURCES):
+    if not _stale(out, sources()):
         return out
     from concurrent.futures import ThreadPoolExecutor
     tag = f"{'asan' if asan else 'ubsan' if sanitize else 'emu'}.{os.getpid()}"   # concurrent builders (multi-process tests) never share a file

@@ -1,43 +1,17 @@
 // logp_san_main.cpp -- TEST-ONLY stand-alone program: the ppg_record_logp kernel source (predpreygrass_amd/csrc/ppg_logp.h) under the
 // CPU wave emulator, built with -fsanitize=address,undefined by tests/test_logp_sanitized.py.  The scan gets exactly the LDS the HIP
-// launch declares (ppg::LOGP_SCAN_LDS_BYTES; the emulator poisons the bytes behind it) and every tensor is a heap block of exactly its
+// launch declares (ppg::ROWS_SCAN_LDS_BYTES; the emulator poisons the bytes behind it) and every tensor is a heap block of exactly its
 // elements -- logp / entropy `capacity` floats, dist capacity * A, the logits B * rows * A, slot [T,B,S], the offsets [B,2] -- so an
 // access outside any of them traps.  Compared with a scalar reference after every call, over: capacities that cut a predator run and a
 // prey run (rows behind the cut have slot -1), capacity 0, slot words corrupted with out-of-range values (ignored, not followed),
 // actions outside [0, A) (PPG_ACTION_UNSET, A, -1, 127: they index nothing), A = 32 and A = 1, rows with one, several and only -inf
 // logits, a NaN, magnitudes of 148, row counts outside the region, a skipped species, and device step words that give t = -1, the last
 // step and steps past the horizon.  Exit status 0 = clean and equal.
-#include "wave_emu/wave_emu.h"
-
-#include <math.h>
-
-#include <vector>
+#include "wave_emu/san_main.h"
 
 #include "../predpreygrass_amd/csrc/ppg_logp.h"
 
-#if defined(__x86_64__)
-__asm__(
-    ".text\n"
-    ".globl ppg_emu_ctx_switch\n"
-    ".type ppg_emu_ctx_switch,@function\n"
-    "ppg_emu_ctx_switch:\n"
-    "  pushq %rbp\n  pushq %rbx\n  pushq %r12\n  pushq %r13\n  pushq %r14\n  pushq %r15\n"
-    "  movq %rsp, (%rdi)\n"
-    "  movq %rsi, %rsp\n"
-    "  popq %r15\n  popq %r14\n  popq %r13\n  popq %r12\n  popq %rbx\n  popq %rbp\n"
-    "  ret\n"
-    ".size ppg_emu_ctx_switch, .-ppg_emu_ctx_switch\n");
-#else
-#error "wave emulator context switch is written for x86-64"
-#endif
-
-static uint64_t g_lcg = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd() {
-    g_lcg = g_lcg * 6364136223846793005ull + 1442695040888963407ull;
-    return (uint32_t)(g_lcg >> 33);
-}
-static int below(int n) { return (int)(rnd() % (uint32_t)n); }
-static float uniform(float lo, float hi) { return lo + (hi - lo) * (float)(rnd() & 0xFFFFFF) / 16777216.0f; }
+constexpr uint64_t SEED = 0x9E3779B97F4A7C15ull;
 
 constexpr int T = 4;
 constexpr uint32_t FILL = 0x5A5A5A5Au;
@@ -177,8 +151,6 @@ static void ref_record(const Case &c, const World &w, const int64_t cap[2], Out 
     }
 }
 
-static void scan_entry(void *arg) { ppg::logp_scan_main(*(const ppg::LogpParams *)arg, wv::emu().lds); }
-static void rows_entry(void *arg) { ppg::logp_rows_main(*(const ppg::LogpParams *)arg); }
 
 static int run(const Case &c) {
     const int S = c.cp + c.cq;
@@ -205,8 +177,8 @@ static int run(const Case &c) {
             K.logp[s] = (float *)got.logp[s].data(); K.entropy[s] = (float *)got.entropy[s].data(); K.dist[s] = got.dist[s].data();
         }
         K.slot = w.slot.data(); K.actions = w.actions.data(); K.off = off.data();
-        wv::run_block(scan_entry, &K, 0, ppg::LOGP_SCAN_LDS_BYTES, 1);
-        for (int b = 0; b < c.B; ++b) wv::run_block(rows_entry, &K, b, 16, 1);
+        run_grid<ppg::LogpParams, ppg::logp_scan_main, ppg::ROWS_SCAN_LDS_BYTES>(K, 1);
+        run_grid<ppg::LogpParams, ppg::logp_rows_main>(K, c.B);
     };
     auto check = [&](const char *what, long long t) {
         bool same = true;
@@ -243,6 +215,7 @@ static int run(const Case &c) {
 }
 
 int main() {
+    lcg_seed(SEED);
     static const Case cases[] = {
         // name                     B  cp   cq  A_p A_q cap_p cap_q corrupt skip
         {"9 / 9 actions",            3, 64, 128,  9,  9,  -1,  -1, false, -1},

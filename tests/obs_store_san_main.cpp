@@ -1,41 +1,16 @@
 // obs_store_san_main.cpp -- TEST-ONLY stand-alone program: the ppg_record_obs kernel source (predpreygrass_amd/csrc/ppg_obs_store.h)
 // under the CPU wave emulator, built with -fsanitize=address,undefined by tests/test_obs_store_sanitized.py.  The scan gets exactly
-// the LDS the HIP launch declares (ppg::OBS_SCAN_LDS_BYTES; the emulator poisons the bytes behind it) and every tensor is a heap block
+// the LDS the HIP launch declares (ppg::ROWS_SCAN_LDS_BYTES; the emulator poisons the bytes behind it) and every tensor is a heap block
 // of exactly its elements -- the stores `capacity` rows, slot [T,B,S] -- so an access outside any of them traps.  Compared with a
 // scalar reference after every call, over: element sizes 8 / 4 / 2 and float64 -> float32, block sizes that leave the destination 0,
 // 4, 8 and 12 bytes off a 16-byte line, stores that are not even 4-byte aligned (the byte loop), single-row runs that end inside the
 // head, capacities that cut a predator run and a prey run, capacity 0, a device step word outside [0, T), and a slot[t-1] corrupted
 // with out-of-range words, which must be ignored, not followed.  Exit status 0 = clean and equal.
-#include "wave_emu/wave_emu.h"
-
-#include <math.h>
-
-#include <vector>
+#include "wave_emu/san_main.h"
 
 #include "../predpreygrass_amd/csrc/ppg_obs_store.h"
 
-#if defined(__x86_64__)
-__asm__(
-    ".text\n"
-    ".globl ppg_emu_ctx_switch\n"
-    ".type ppg_emu_ctx_switch,@function\n"
-    "ppg_emu_ctx_switch:\n"
-    "  pushq %rbp\n  pushq %rbx\n  pushq %r12\n  pushq %r13\n  pushq %r14\n  pushq %r15\n"
-    "  movq %rsp, (%rdi)\n"
-    "  movq %rsi, %rsp\n"
-    "  popq %r15\n  popq %r14\n  popq %r13\n  popq %r12\n  popq %rbx\n  popq %rbp\n"
-    "  ret\n"
-    ".size ppg_emu_ctx_switch, .-ppg_emu_ctx_switch\n");
-#else
-#error "wave emulator context switch is written for x86-64"
-#endif
-
-static uint64_t g_lcg = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd() {
-    g_lcg = g_lcg * 6364136223846793005ull + 1442695040888963407ull;
-    return (uint32_t)(g_lcg >> 33);
-}
-static int below(int n) { return (int)(rnd() % (uint32_t)n); }
+constexpr uint64_t SEED = 0x9E3779B97F4A7C15ull;
 
 constexpr int T = 4;
 
@@ -144,8 +119,6 @@ static void ref_record(const Case &c, World &w, const int64_t cap[2], Store &x, 
     }
 }
 
-static void scan_entry(void *arg) { ppg::obs_scan_main(*(const ppg::ObsStoreParams *)arg, wv::emu().lds); }
-static void rows_entry(void *arg) { ppg::obs_rows_main(*(const ppg::ObsStoreParams *)arg); }
 
 static int run(const Case &c) {
     const int S = c.cp + c.cq;
@@ -173,8 +146,8 @@ static int run(const Case &c) {
         }
         K.slot = got.slot.data(); K.cursor = got.cursor; K.base = base.data();
         K.actions = with_actions ? w.actions.data() : nullptr;
-        wv::run_block(scan_entry, &K, 0, ppg::OBS_SCAN_LDS_BYTES, 1);
-        for (int b = 0; b < c.B; ++b) wv::run_block(rows_entry, &K, b, 16, 1);
+        run_grid<ppg::ObsStoreParams, ppg::obs_scan_main, ppg::ROWS_SCAN_LDS_BYTES>(K, 1);
+        run_grid<ppg::ObsStoreParams, ppg::obs_rows_main>(K, c.B);
     };
     auto check = [&](const char *what, int t) {
         if (!got.same(want)) { fprintf(stderr, "%s, %s %d: the stores differ (cursor %lld %lld %lld %lld, want %lld %lld %lld %lld)\n", c.name, what, t,
@@ -211,6 +184,7 @@ static int run(const Case &c) {
 }
 
 int main() {
+    lcg_seed(SEED);
     static const Case cases[] = {
         // name                  B  cp   cq  blk_p blk_q src dst cap_p cap_q shift few
         {"f64 7x7 / 9x9",         3, 64, 128, 196, 324, 8, 8, -1, -1, 0, false},     // aligned: the 16-byte main loop

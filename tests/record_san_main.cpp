@@ -4,36 +4,11 @@
 // poisons the bytes behind it, and every table is a heap block of exactly its elements -- the trajectory buffers [T,B,S] with
 // T = 3 -- so an access outside either traps.  Steps 0, 1, 2 and launches whose device step word is outside [0, T) are compared with
 // a scalar reference.  Exit status 0 = clean and equal.
-#include "wave_emu/wave_emu.h"
-
-#include <math.h>
-
-#include <vector>
+#include "wave_emu/san_main.h"
 
 #include "../predpreygrass_amd/csrc/ppg_record.h"
 
-#if defined(__x86_64__)
-__asm__(
-    ".text\n"
-    ".globl ppg_emu_ctx_switch\n"
-    ".type ppg_emu_ctx_switch,@function\n"
-    "ppg_emu_ctx_switch:\n"
-    "  pushq %rbp\n  pushq %rbx\n  pushq %r12\n  pushq %r13\n  pushq %r14\n  pushq %r15\n"
-    "  movq %rsp, (%rdi)\n"
-    "  movq %rsi, %rsp\n"
-    "  popq %r15\n  popq %r14\n  popq %r13\n  popq %r12\n  popq %rbx\n  popq %rbp\n"
-    "  ret\n"
-    ".size ppg_emu_ctx_switch, .-ppg_emu_ctx_switch\n");
-#else
-#error "wave emulator context switch is written for x86-64"
-#endif
-
-static uint64_t g_lcg = 0x2545F4914F6CDD1Dull;
-static uint32_t rnd() {
-    g_lcg = g_lcg * 6364136223846793005ull + 1442695040888963407ull;
-    return (uint32_t)(g_lcg >> 33);
-}
-static int below(int n) { return (int)(rnd() % (uint32_t)n); }
+constexpr uint64_t SEED = 0x2545F4914F6CDD1Dull;
 
 constexpr int T = 3;
 
@@ -138,7 +113,6 @@ static void ref_store(const World &w, const std::vector<int16_t> &next, int t, B
     }
 }
 
-static void entry(void *arg) { ppg::record_main(*(const ppg::RecordParams *)arg, wv::emu().lds); }
 
 static int run(int cp, int cq) {
     const int B = 2;
@@ -164,7 +138,7 @@ static int run(int cp, int cq) {
         K.row_reward = (const uint64_t *)w.row_reward.data(); K.reward = (uint64_t *)got.reward.data();
         K.in_use = got.in_use.data(); K.terminated = got.terminated.data(); K.truncated = got.truncated.data();
         K.traj_next = got.next_row.data();
-        for (int b = 0; b < B; ++b) wv::run_block(entry, &K, b, ppg::LINK_LDS_BYTES, 1);
+        run_grid<ppg::RecordParams, ppg::record_main, ppg::LINK_LDS_BYTES>(K, B);
         valid = 1;
     };
     auto check = [&](const char *what) {
@@ -195,6 +169,7 @@ static int run(int cp, int cq) {
 }
 
 int main() {
+    lcg_seed(SEED);
     int bad = 0;
     bad |= run(64, 64);
     bad |= run(64, 128);

@@ -5,21 +5,7 @@
 
 #include "../../predpreygrass_amd/csrc/ppg_host.h"
 
-#if defined(__x86_64__)
-__asm__(
-    ".text\n"
-    ".globl ppg_emu_ctx_switch\n"
-    ".type ppg_emu_ctx_switch,@function\n"
-    "ppg_emu_ctx_switch:\n"
-    "  pushq %rbp\n  pushq %rbx\n  pushq %r12\n  pushq %r13\n  pushq %r14\n  pushq %r15\n"
-    "  movq %rsp, (%rdi)\n"
-    "  movq %rsi, %rsp\n"
-    "  popq %r15\n  popq %r14\n  popq %r13\n  popq %r12\n  popq %rbx\n  popq %rbp\n"
-    "  ret\n"
-    ".size ppg_emu_ctx_switch, .-ppg_emu_ctx_switch\n");
-#else
-#error "wave emulator context switch is written for x86-64"
-#endif
+#include "ctx_switch.h"
 
 struct EmuLaunch {
     const ppg::KParams *P;
@@ -112,18 +98,12 @@ static int backend_launch(ppg_handle *h, int mode, const ppg::KParams &P, void *
     return PPG_OK;
 }
 
-static void pack_scan_entry(void *arg) { ppg::pack_scan_main(*(const ppg::PackParams *)arg, wv::emu().lds); }
-static void pack_rows_entry(void *arg) { ppg::pack_rows_main(*(const ppg::PackParams *)arg); }
+// (ppg_emu_rows and the launches of the later learner-side calls: ppg_host.h)
 static int backend_pack(ppg_handle *, const ppg::PackParams &K, void *) {
-    wv::run_block(pack_scan_entry, (void *)&K, 0, 512, 1);
-    for (int e = 0; e < K.n_envs; ++e) wv::run_block(pack_rows_entry, (void *)&K, e, 16, 1);
-    return PPG_OK;
+    ppg_emu_rows<ppg::PackParams, ppg::pack_scan_main, ppg::ROWS_SCAN_LDS_BYTES>(K, 1);
+    return ppg_emu_rows<ppg::PackParams, ppg::pack_rows_main>(K, K.n_envs);
 }
-static void fetch_entry(void *arg) { ppg::fetch_main(*(const ppg::FetchParams *)arg, wv::emu().lds); }
-static int backend_fetch(ppg_handle *, const ppg::FetchParams &K, void *) {
-    for (int e = 0; e < K.n_envs; ++e) wv::run_block(fetch_entry, (void *)&K, e, 1024, 1);
-    return PPG_OK;
-}
+static int backend_fetch(ppg_handle *, const ppg::FetchParams &K, void *) { return ppg_emu_rows<ppg::FetchParams, ppg::fetch_main, 1024>(K, K.n_envs); }
 static int backend_copy(ppg_handle *, void *dst, const void *src, size_t bytes, bool, void *) {
     memcpy(dst, src, bytes);
     return PPG_OK;
