@@ -53,6 +53,27 @@ def _alloc_on(device, stream, fn):
     return out
 
 
+def capture_graph(device, body):
+    """body() captured into a torch.cuda.CUDAGraph, after one uncaptured pass on a fresh side stream ordered behind the current stream
+    (lazy allocations and attribute calls of the library and of the env must not fall into the capture); the current stream waits for
+    that pass and the device is synchronised before the capture starts."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        body()
+    torch.cuda.current_stream(device).wait_stream(side)
+    torch.cuda.synchronize(device)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        body()
+    return graph
+
+
+def _ptr(x):
+    """The address of a tensor as a launch argument; None stays None."""
+    return None if x is None else C.c_void_p(x.data_ptr())
+
+
 class BatchedPredPreyGrass:
     """Tensor API.
 
@@ -197,6 +218,7 @@ class BatchedPredPreyGrass:
         self.obs_pred = self._obs_tensor((B, self.pred_capacity, self.obs_channels_pred, self.Rp, self.Rp), seed_salt=1)
         self.obs_prey = self._obs_tensor((B, self.prey_capacity, self.obs_channels_prey, self.Rq, self.Rq), seed_salt=2)
         self.actions = torch.full((B, S), _abi.ACTION_NONE, dtype=torch.int8, device=dev)
+        self._row_index = torch.arange(S, device=dev, dtype=torch.int32).unsqueeze(0)   # (live_mask()'s row numbers)
 
     def _obs_tensor(self, shape, seed_salt=0):
         """An observation tensor: from torch's allocator, or (obs_spread > 1, HIP library) on spread physical pages."""
@@ -232,11 +254,8 @@ class BatchedPredPreyGrass:
         dev_index = self.device.index if self.device.type == "cuda" else 0
         rc = create_fn(C.byref(c), self.batch_size, dev_index, C.byref(bufs), C.byref(self._handle))
         if rc != 0:
-            msg = self._lib.ppg_last_error(None).decode()
-            self._handle = None
-            if rc == -1:
-                raise ValueError(msg)  # e.g. "Cannot place more unique positions than grid cells."
-            raise RuntimeError(f"ppg_create failed ({rc}): {msg}")
+            self._handle = None   # (the message is then the library's, not a handle's)
+        self._check(rc, "ppg_create", value_error=True)  # e.g. "Cannot place more unique positions than grid cells."
         self.lds_bytes = int(self._lib.ppg_lds_bytes(self._handle))
 
     # ------------------------------------------------------------------
@@ -259,9 +278,13 @@ class BatchedPredPreyGrass:
             return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         return C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
 
-    def _check(self, rc, what):
+    def _check(self, rc, what, value_error=False):
+        """Raise unless rc is 0.  value_error: -1 is the library's refusal of an argument and raises ValueError with its message alone."""
         if rc != 0:
-            raise RuntimeError(f"{what} failed ({rc}): {self._lib.ppg_last_error(self._handle).decode()}")
+            msg = self._lib.ppg_last_error(self._handle).decode()
+            if value_error and rc == -1:
+                raise ValueError(msg)
+            raise RuntimeError(f"{what} failed ({rc}): {msg}")
 
     def _tensor_arg(self, name, x, dtypes, shape):
         """The pointer of a tensor argument of a launch; ValueError unless it is a contiguous tensor of one of `dtypes` and of `shape`
@@ -347,10 +370,7 @@ class BatchedPredPreyGrass:
         init = _abi.PpgInitState()
         init.pred_xy, init.prey_xy, init.grass_xy = (a.ctypes.data for a in arrays)
         init.episode = int(episode)
-        rc = self._lib.ppg_reset_from_state(self._handle, C.byref(init), self._stream())
-        if rc == -1:
-            raise ValueError(self._lib.ppg_last_error(self._handle).decode())
-        self._check(rc, "ppg_reset_from_state")
+        self._check(self._lib.ppg_reset_from_state(self._handle, C.byref(init), self._stream()), "ppg_reset_from_state", value_error=True)
         return self
 
     def set_wave_plan(self, waves=0, helper_min_rows=0, coop_envs=0):
@@ -418,13 +438,17 @@ class BatchedPredPreyGrass:
         this call is still in use (it carries its last observation and reward) and is dropped by the next call, like the
         reference keeps a dead agent in `agents` until the next step (predpreygrass_rllib_env.py:222-225,459-461)."""
         self.step(actions, **kw)
-        n_pred = self.env_state[:, _abi.ENV_N_PRED_ROWS:_abi.ENV_N_PRED_ROWS + 1]
-        n_prey = self.env_state[:, _abi.ENV_N_PREY_ROWS:_abi.ENV_N_PREY_ROWS + 1]
-        slot = torch.arange(self.S, device=self.device, dtype=torch.int32).unsqueeze(0)
-        live = torch.where(slot < self.pred_capacity, slot < n_pred, slot - self.pred_capacity < n_prey)
-        flags = self.row_flags
+        live, flags = self.live_mask(), self.row_flags
         return (self.obs_pred, self.obs_prey, self.row_reward, ((flags & _abi.ROW_DIED) != 0) & live,
                 ((flags & _abi.ROW_TRUNC) != 0) & live, live, self.row_id)
+
+    def live_mask(self):
+        """Which rows are in use: bool [B,S] on the device, nothing read back -- row r < pred_capacity iff r < the env's predator row
+        count, row pred_capacity + j iff j < its prey row count (a count outside [0, capacity] acts as if clamped to it)."""
+        n_pred = self.env_state[:, _abi.ENV_N_PRED_ROWS:_abi.ENV_N_PRED_ROWS + 1]
+        n_prey = self.env_state[:, _abi.ENV_N_PREY_ROWS:_abi.ENV_N_PREY_ROWS + 1]
+        slot, cp = self._row_index, self.pred_capacity
+        return torch.where(slot < cp, slot < n_pred, slot - cp < n_prey)
 
     def rollout(self, n_steps, actions=None, random_actions=False, auto_reset=False, stream=None):
         """`n_steps` transitions in ONE kernel launch (state stays on chip between steps): the same result
@@ -449,8 +473,7 @@ class BatchedPredPreyGrass:
         stream (optional): launch on this torch.cuda.Stream instead of torch's current stream; the two tensors are then allocated
         on that stream too, and whoever reads them from another stream orders itself behind it."""
         prev_row, next_row = self._link_tensors(stream)
-        self._check(self._lib.ppg_link(self._handle, C.c_void_p(prev_row.data_ptr()), C.c_void_p(next_row.data_ptr()),
-                                       self._stream(stream)), "ppg_link")
+        self._check(self._lib.ppg_link(self._handle, _ptr(prev_row), _ptr(next_row), self._stream(stream)), "ppg_link")
         return prev_row, next_row
 
     def _link_tensors(self, stream=None):
@@ -474,8 +497,8 @@ class BatchedPredPreyGrass:
         buf = _abi.PpgRecordBuffers(shape[0], reward.data_ptr(), in_use.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
                                     next_row.data_ptr())
         prev_row, link_next = self._link_tensors(stream)
-        self._check(self._lib.ppg_record(self._handle, C.byref(buf), step, flags, C.c_void_p(prev_row.data_ptr()),
-                                         C.c_void_p(link_next.data_ptr()), self._stream(stream)), "ppg_record")
+        self._check(self._lib.ppg_record(self._handle, C.byref(buf), step, flags, _ptr(prev_row), _ptr(link_next),
+                                         self._stream(stream)), "ppg_record")
         return prev_row, link_next
 
     def _step_index(self, t, T):
@@ -489,6 +512,31 @@ class BatchedPredPreyGrass:
             raise ValueError(f"t = {step} is outside [0, {T})")
         return step, False
 
+    def _store_args(self, store):
+        """What record_obs(), record_logp() and backward_samples() share of a sample store: (the `PpgObsStore` with `horizon`, `slot`
+        and `capacity[2]` filled, the anchor address).  Each call refuses what only it knows first (a flag, a missing tensor list, a
+        tuple that is no pair); then the arguments are checked in ONE order: `store.slot`, the capacities, the per-species tensors --
+        predators then prey, per species in the order of the struct's fields --, `store.cursor`, logits or values, the step, `actions`.
+        The anchor is `store.slot`, which is never empty: the address given for an EMPTY tensor, which has none (capacity 0, nothing is
+        addressed through it)."""
+        T = int(store.horizon)
+        st = _abi.PpgObsStore()
+        st.horizon = T
+        st.slot = anchor = self._tensor_arg("store.slot", store.slot, (torch.int32,), (T, self.batch_size, self.S)).value
+        for s in (0, 1):
+            capacity = int(store.capacity[s])
+            if capacity < 0:
+                raise ValueError(f"store.capacity[{s}] = {capacity} < 0")
+            st.capacity[s] = capacity
+        return st, anchor
+
+    def _rows_arg(self, name, x, dtypes, shape, capacity, anchor, noun="rows"):
+        """The address of a per-species tensor [rows >= capacity, *shape] of a sample store (or the anchor: see _store_args)."""
+        ptr = self._tensor_arg(name, x, dtypes, (None,) + shape)
+        if x.shape[0] < capacity:
+            raise ValueError(f"{name} has {x.shape[0]} {noun}, fewer than the capacity {capacity}")
+        return ptr.value or anchor
+
     def record_obs(self, store, t, actions=None, f32=False, stream=None):
         """Append the observation rows in use of this call's output, as step t, to a compact per-species sample store
         (`ppg_record_obs`, include/ppg.h: order, overflow and the elements written are stated there), in two launches.
@@ -498,35 +546,22 @@ class BatchedPredPreyGrass:
         t: as in record().  actions: the int8 [B,S] tensor the env's last step was given (they answer the observations stored by the
         previous record_obs()), or None -- no actions are stored (device-drawn random actions).
         stream (optional): launch on this torch.cuda.Stream instead of torch's current stream."""
-        T, B, S = int(store.horizon), self.batch_size, self.S
         if f32 and self.obs_dtype == torch.bfloat16:
             raise ValueError("f32=True is for float64 (and float32) observations, not bfloat16")
-        dtype = torch.float32 if f32 and self.obs_dtype == torch.float64 else self.obs_dtype
-        cursor = self._tensor_arg("store.cursor", store.cursor, (torch.int64,), (4,))
-
-        def rows(name, x, dtypes, shape, capacity):
-            ptr = self._tensor_arg(name, x, dtypes, (None,) + shape)
-            if x.shape[0] < capacity:
-                raise ValueError(f"{name} has {x.shape[0]} rows, fewer than the capacity {capacity}")
-            return ptr.value or cursor.value   # (an empty tensor has no address: capacity 0, nothing is addressed through it)
-        st = _abi.PpgObsStore()
-        st.horizon = T
         if actions is not None and store.action is None:
             raise ValueError("actions were given but the store keeps none")
+        dtype = torch.float32 if f32 and self.obs_dtype == torch.float64 else self.obs_dtype
+        st, anchor = self._store_args(store)
         for s, src in enumerate((self.obs_pred, self.obs_prey)):
-            capacity = int(store.capacity[s])
-            if capacity < 0:
-                raise ValueError(f"store.capacity[{s}] = {capacity} < 0")
-            st.capacity[s] = capacity
-            st.obs[s] = rows(f"store.obs[{s}]", store.obs[s], (dtype,), tuple(src.shape[2:]), capacity)
-            st.sample[s] = rows(f"store.sample[{s}]", store.sample[s], (torch.int32,), (), capacity)
+            capacity = st.capacity[s]
+            st.obs[s] = self._rows_arg(f"store.obs[{s}]", store.obs[s], (dtype,), tuple(src.shape[2:]), capacity, anchor)
+            st.sample[s] = self._rows_arg(f"store.sample[{s}]", store.sample[s], (torch.int32,), (), capacity, anchor)
             if store.action is not None:
-                st.action[s] = rows(f"store.action[{s}]", store.action[s], (torch.int8,), (), capacity)
-        st.slot = self._tensor_arg("store.slot", store.slot, (torch.int32,), (T, B, S)).value
-        st.cursor = cursor.value
-        step, on_device = self._step_index(t, T)
+                st.action[s] = self._rows_arg(f"store.action[{s}]", store.action[s], (torch.int8,), (), capacity, anchor)
+        st.cursor = self._tensor_arg("store.cursor", store.cursor, (torch.int64,), (4,)).value
+        step, on_device = self._step_index(t, st.horizon)
         flags = (_abi.OBS_STEP_ON_DEVICE if on_device else 0) | (_abi.OBS_F32 if f32 else 0)
-        act = None if actions is None else self._tensor_arg("actions", actions, (torch.int8,), (B, S))
+        act = None if actions is None else self._tensor_arg("actions", actions, (torch.int8,), (self.batch_size, self.S))
         self._check(self._lib.ppg_record_obs(self._handle, C.byref(st), step, flags, act, self._stream(stream)), "ppg_record_obs")
         return store
 
@@ -543,37 +578,26 @@ class BatchedPredPreyGrass:
         logits: (logits_pred, logits_prey), float32 [B * capacity_s, A_s] as `FusedPolicy.act()` fills them; either may be None -- that
         species is skipped.  actions: the int8 [B,S] tensor act() filled (default: `env.actions`).
         stream (optional): launch on this torch.cuda.Stream instead of torch's current stream."""
-        T, B, S = int(store.horizon), self.batch_size, self.S
         if getattr(store, "logp", None) is None:
             raise ValueError("the store keeps no log-probabilities: ObservationStore(..., logp=(A_pred, A_prey))")
         if len(logits) != 2:
             raise ValueError("logits must be the pair (logits_pred, logits_prey); either may be None")
-        anchor = self._tensor_arg("store.slot", store.slot, (torch.int32,), (T, B, S))
-
-        def rows(name, x, shape, capacity):
-            ptr = self._tensor_arg(name, x, (torch.float32,), (None,) + shape)
-            if x.shape[0] < capacity:
-                raise ValueError(f"{name} has {x.shape[0]} rows, fewer than the capacity {capacity}")
-            return ptr.value or anchor.value   # (an empty tensor has no address: capacity 0, nothing is addressed through it)
-        st, out = _abi.PpgObsStore(), _abi.PpgLogpStore()
-        st.horizon, st.slot = T, anchor.value
-        lg = [None, None]
+        st, anchor = self._store_args(store)
+        out, f32, lg = _abi.PpgLogpStore(), (torch.float32,), [None, None]
         for s, cap in enumerate((self.pred_capacity, self.prey_capacity)):
-            capacity, A = int(store.capacity[s]), int(store.n_actions[s])
-            if capacity < 0:
-                raise ValueError(f"store.capacity[{s}] = {capacity} < 0")
+            capacity, A = st.capacity[s], int(store.n_actions[s])
             if not 1 <= A <= 32:
                 raise ValueError(f"store.n_actions[{s}] = {A} is outside 1..32")
-            st.capacity[s], out.n_actions[s] = capacity, A
-            out.logp[s] = rows(f"store.logp[{s}]", store.logp[s], (), capacity)
+            out.n_actions[s] = A
+            out.logp[s] = self._rows_arg(f"store.logp[{s}]", store.logp[s], f32, (), capacity, anchor)
             if store.entropy is not None:
-                out.entropy[s] = rows(f"store.entropy[{s}]", store.entropy[s], (), capacity)
+                out.entropy[s] = self._rows_arg(f"store.entropy[{s}]", store.entropy[s], f32, (), capacity, anchor)
             if store.dist is not None:
-                out.dist[s] = rows(f"store.dist[{s}]", store.dist[s], (A,), capacity)
+                out.dist[s] = self._rows_arg(f"store.dist[{s}]", store.dist[s], f32, (A,), capacity, anchor)
             if logits[s] is not None:
-                lg[s] = self._tensor_arg(f"logits[{s}]", logits[s], (torch.float32,), (B * cap, A))
-        step, on_device = self._step_index(t, T)
-        act = self._tensor_arg("actions", self.actions if actions is None else actions, (torch.int8,), (B, S))
+                lg[s] = self._tensor_arg(f"logits[{s}]", logits[s], f32, (self.batch_size * cap, A))
+        step, on_device = self._step_index(t, st.horizon)
+        act = self._tensor_arg("actions", self.actions if actions is None else actions, (torch.int8,), (self.batch_size, self.S))
         self._check(self._lib.ppg_record_logp(self._handle, C.byref(st), C.byref(out), step, _abi.LOGP_STEP_ON_DEVICE if on_device else 0,
                                               lg[0], lg[1], act, self._stream(stream)), "ppg_record_logp")
         return store
@@ -596,13 +620,10 @@ class BatchedPredPreyGrass:
                                       **({"values": values} if want_a else {}))
         G, A = _alloc_on(self.device, stream, lambda: tuple(
             torch.empty(shape, dtype=torch.float64, device=self.device) if want else None for want in (returns, want_a)))
-
-        def ptr(x):
-            return None if x is None else C.c_void_p(x.data_ptr())
-        self._check(self._lib.ppg_backward(self._handle, shape[0], ptr(reward), ptr(next_row), ptr(in_use), ptr(terminated),
-                                           ptr(truncated), ptr(values) if want_a else None,
+        self._check(self._lib.ppg_backward(self._handle, shape[0], _ptr(reward), _ptr(next_row), _ptr(in_use), _ptr(terminated),
+                                           _ptr(truncated), _ptr(values) if want_a else None,
                                            _abi.F32 if want_a and values.dtype == torch.float32 else _abi.F64,
-                                           float(gamma), float(lam), ptr(G), ptr(A), self._stream(stream)), "ppg_backward")
+                                           float(gamma), float(lam), _ptr(G), _ptr(A), self._stream(stream)), "ppg_backward")
         return G, A
 
     def backward_samples(self, store, reward, next_row, in_use, terminated, truncated, gamma, lam=1.0, values=(None, None),
@@ -624,43 +645,31 @@ class BatchedPredPreyGrass:
         if len(values) != 2:
             raise ValueError("values must be the pair (v_pred, v_prey); either may be None")
         shape = self._trajectory_args(reward=reward, next_row=next_row, in_use=in_use, terminated=terminated, truncated=truncated)
-        horizon, B, S = int(store.horizon), self.batch_size, self.S
-        if shape[0] > horizon:
-            raise ValueError(f"{shape[0]} steps, but the store's horizon is {horizon}")
-        st, tg = _abi.PpgObsStore(), _abi.PpgSampleTargets()
-        st.horizon = horizon
-        st.slot = self._tensor_arg("store.slot", store.slot, (torch.int32,), (horizon, B, S)).value
+        if shape[0] > int(store.horizon):
+            raise ValueError(f"{shape[0]} steps, but the store's horizon is {int(store.horizon)}")
         given = [v for v in values if v is not None]
         if any(v.dtype != given[0].dtype for v in given):
             raise ValueError("values of the two species must have one dtype")
-        capacity = [int(c) for c in store.capacity]
+        st, anchor = self._store_args(store)
+        tg, capacity = _abi.PpgSampleTargets(), tuple(st.capacity)
         for s, v in enumerate(values):
-            if capacity[s] < 0:
-                raise ValueError(f"store.capacity[{s}] = {capacity[s]} < 0")
-            st.capacity[s] = capacity[s]
             if v is not None:
-                ptr = self._tensor_arg(f"values[{s}]", v, self._TRAJECTORY_DTYPES["values"], (None,))
-                if v.shape[0] < capacity[s]:
-                    raise ValueError(f"values[{s}] has {v.shape[0]} elements, fewer than the capacity {capacity[s]}")
-                tg.values[s] = ptr.value or st.slot   # (an empty tensor has no address: capacity 0, nothing is addressed through it)
+                tg.values[s] = self._rows_arg(f"values[{s}]", v, self._TRAJECTORY_DTYPES["values"], (), capacity[s], anchor, "elements")
 
         def outputs():
             pair = lambda: [torch.zeros((n,), dtype=torch.float32, device=self.device) for n in capacity]
             return (pair() if advantages else None, pair() if returns else None,
-                    torch.empty((B, 2, 3), dtype=torch.float64, device=self.device) if stats else None)
+                    torch.empty((self.batch_size, 2, 3), dtype=torch.float64, device=self.device) if stats else None)
         adv, ret, moments = _alloc_on(self.device, stream, outputs)
-        for s in (0, 1):
+        for s in (0, 1):   # (the outputs of a species of capacity 0 are empty: anchored like its inputs)
             if adv is not None:
-                tg.advantage[s] = adv[s].data_ptr() or st.slot
+                tg.advantage[s] = adv[s].data_ptr() or anchor
             if ret is not None:
-                tg.returns[s] = ret[s].data_ptr() or st.slot
+                tg.returns[s] = ret[s].data_ptr() or anchor
         if moments is not None:
             tg.stats = moments.data_ptr()
-
-        def ptr(x):
-            return C.c_void_p(x.data_ptr())
-        self._check(self._lib.ppg_backward_samples(self._handle, shape[0], ptr(reward), ptr(next_row), ptr(in_use), ptr(terminated),
-                                                   ptr(truncated), C.byref(st), C.byref(tg),
+        self._check(self._lib.ppg_backward_samples(self._handle, shape[0], _ptr(reward), _ptr(next_row), _ptr(in_use), _ptr(terminated),
+                                                   _ptr(truncated), C.byref(st), C.byref(tg),
                                                    _abi.F32 if given and given[0].dtype == torch.float32 else _abi.F64,
                                                    float(gamma), float(lam), self._stream(stream)), "ppg_backward_samples")
         return adv, ret, moments
@@ -669,7 +678,7 @@ class BatchedPredPreyGrass:
         """grid_world_state of every env: float64 [B,4,G,G] (predpreygrass_rllib_env.py:124)."""
         G = self.grid_size
         out = torch.empty((self.batch_size, 4, G, G), dtype=torch.float64, device=self.device)
-        self._check(self._lib.ppg_export_grid(self._handle, C.c_void_p(out.data_ptr()), self._stream()), "ppg_export_grid")
+        self._check(self._lib.ppg_export_grid(self._handle, _ptr(out), self._stream()), "ppg_export_grid")
         return out
 
     def export_state(self, b=0) -> bytes:
@@ -684,10 +693,7 @@ class BatchedPredPreyGrass:
         """Write an image from `export_state` into env b (`ppg_import_state`, predpreygrass_rllib_env.py:788-804); the
         geometry of the handle it came from must match.  Call `observe()` afterwards for the observations."""
         buf = C.create_string_buffer(bytes(blob), len(blob))
-        rc = self._lib.ppg_import_state(self._handle, int(b), buf, len(blob), self._stream())
-        if rc == -1:
-            raise ValueError(self._lib.ppg_last_error(self._handle).decode())
-        self._check(rc, "ppg_import_state")
+        self._check(self._lib.ppg_import_state(self._handle, int(b), buf, len(blob), self._stream()), "ppg_import_state", value_error=True)
         return self
 
     # ------------------------------------------------------------------

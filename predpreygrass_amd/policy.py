@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .batched import _alloc_on
+from .batched import _alloc_on, capture_graph
 
 
 class _Named(torch.nn.Module):
@@ -276,10 +276,7 @@ class FusedPolicy:
                     continue
                 if net is None:
                     raise ValueError(f"logits[{t}] was given but the policy has no network for that species")
-                shape = (cap(t), net.n_actions)
-                if x.dtype != torch.float32 or tuple(x.shape) != shape or x.device != self.device or not x.is_contiguous():
-                    raise ValueError(f"logits[{t}] must be a contiguous torch.float32 tensor [{shape[0]},{shape[1]}] on {self.device}, not a"
-                                     f"{'' if x.is_contiguous() else ' non-contiguous'} {x.dtype} tensor {list(x.shape)} on {x.device}")
+                envs[0]._tensor_arg(f"logits[{t}]", x, (torch.float32,), (cap(t), net.n_actions))
                 lg[t] = x
         elif want_logits:
             # zero-filled on the stream the kernels run on, so that the fill cannot race with their writes
@@ -335,16 +332,7 @@ class GraphedPolicyStep:
             fused.act(env, sample=sample, seed=self.seed)
             env.step(env.actions, auto_reset=auto_reset)
             self.seed.add_(self._one)
-        # (one uncaptured pass on a side stream first: lazy allocations and attribute calls of the library must not fall into the capture)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            body()
+        self.graph = capture_graph(dev, body)
 
     def replay(self, n: int = 1):
         for _ in range(n):

@@ -93,6 +93,7 @@ import types
 import torch
 
 from . import _abi
+from .batched import capture_graph
 
 
 class ObservationStore:
@@ -166,15 +167,12 @@ class ObservationStore:
             raise ValueError("the store keeps no log-probabilities: ObservationStore(..., logp=(A_pred, A_prey))")
         if not 0 <= t < self.horizon:
             raise ValueError(f"t = {t} is outside [0, {self.horizon})")
-        dev = env.device
-        actions = env.actions if actions is None else actions
-        for s, (first, cap, word) in enumerate(((0, env.pred_capacity, _abi.ENV_N_PRED_ROWS),
-                                                (env.pred_capacity, env.prey_capacity, _abi.ENV_N_PREY_ROWS))):
+        actions, live = env.actions if actions is None else actions, env.live_mask()
+        for s, (first, cap) in enumerate(((0, env.pred_capacity), (env.pred_capacity, env.prey_capacity))):
             if logits[s] is None:
                 continue
             A = self.n_actions[s]
-            n = env.env_state[:, word:word + 1].clamp(0, cap)
-            b, j = (torch.arange(cap, device=dev).unsqueeze(0) < n).nonzero(as_tuple=True)   # env-major, rows ascending: the logits' order
+            b, j = live[:, first:first + cap].nonzero(as_tuple=True)   # env-major, rows ascending: the logits' order
             k = self.slot[t][b, first + j].long()
             ok = (k >= 0) & (k < self.capacity[s])
             row, k, a = logits[s][:b.numel()][ok], k[ok], actions[b, first + j][ok].long()
@@ -201,11 +199,9 @@ class ObservationStore:
             raise ValueError(f"t = {t} is outside [0, {self.horizon})")
         B, S, dev = env.batch_size, env.S, env.device
         cursor = self.cursor.tolist()
-        slot_t = torch.full((B, S), -1, dtype=torch.int32, device=dev)
-        for s, (first, cap, src, word) in enumerate(((0, env.pred_capacity, env.obs_pred, _abi.ENV_N_PRED_ROWS),
-                                                     (env.pred_capacity, env.prey_capacity, env.obs_prey, _abi.ENV_N_PREY_ROWS))):
-            n = env.env_state[:, word:word + 1].clamp(0, cap)
-            b, j = (torch.arange(cap, device=dev).unsqueeze(0) < n).nonzero(as_tuple=True)   # env-major, rows ascending
+        slot_t, live = torch.full((B, S), -1, dtype=torch.int32, device=dev), env.live_mask()
+        for s, (first, cap, src) in enumerate(((0, env.pred_capacity, env.obs_pred), (env.pred_capacity, env.prey_capacity, env.obs_prey))):
+            b, j = live[:, first:first + cap].nonzero(as_tuple=True)   # env-major, rows ascending
             k = cursor[s] + torch.arange(b.numel(), device=dev)
             keep = k < self.capacity[s]
             b, j, k = b[keep], j[keep], k[keep]
@@ -238,7 +234,6 @@ class AgentTrajectories:
         self.terminated = torch.zeros((T, B, S), dtype=torch.bool, device=dev)
         self.truncated = torch.zeros((T, B, S), dtype=torch.bool, device=dev)
         self.next_row = torch.full((T, B, S), -1, dtype=torch.int16, device=dev)
-        self._slot = torch.arange(S, device=dev, dtype=torch.int32).unsqueeze(0)
         # step_on_device: the step index lives in `t_dev` (int32 [1] on the device), read by the record kernel when it runs and
         # counted up behind it on the same stream -- no host value in the launch, so step + record can be captured and replayed
         # (GraphedCollector).  A record() past the horizon then writes nothing (and still links) instead of raising.
@@ -287,20 +282,24 @@ class AgentTrajectories:
         With a store (obs_rows) two more launches follow with the same step index: `env.record_obs()` appends the observation rows in
         use; actions: the int8 [B,S] tensor the step was given, stored as the actions of the previous record()'s samples (None: the
         actions stay ACTION_UNSET, e.g. device-drawn random actions)."""
-        env = self.env
-        if self.step_on_device:
-            env.record(self.reward, self.in_use, self.terminated, self.truncated, self.next_row, self.t_dev)
-            if self.store is not None:
-                self.store.record(self.t_dev, actions)
-            self.t_dev.add_(1)
-            return self
-        if self._t >= self.horizon:
+        if not self.step_on_device and self._t >= self.horizon:
             raise RuntimeError(f"the trajectory is full ({self.horizon} steps): clear() it")
-        env.record(self.reward, self.in_use, self.terminated, self.truncated, self.next_row, self._t)
+        t = self.t_dev if self.step_on_device else self._t
+        self.env.record(self.reward, self.in_use, self.terminated, self.truncated, self.next_row, t)
         if self.store is not None:
-            self.store.record(self._t, actions)
-        self._t += 1
+            self.store.record(t, actions)
+        if self.step_on_device:
+            self.t_dev.add_(1)
+        else:
+            self._t += 1
         return self
+
+    def _need_store(self, what, logp=False):
+        """RuntimeError unless the trajectory has a store (logp: one that keeps log-probabilities): what `what` refuses without it."""
+        if self.store is None or (logp and self.store.logp is None):
+            hint = "AgentTrajectories(..., obs_rows=(n_pred, n_prey), logp=(A_pred, A_prey))" if logp else \
+                "a store: AgentTrajectories(..., obs_rows=(n_pred, n_prey))"
+            raise RuntimeError(f"{what}() needs {hint}")
 
     def record_policy(self, logits, actions=None):
         """Store what the behaviour policy thought of the samples of the LAST record(): call it between `fused.act(env, ...,
@@ -308,8 +307,7 @@ class AgentTrajectories:
         the tensor it wrote (default `env.actions`).  Two launches (`env.record_logp()`), nothing read back.  The step is t - 1 on the
         host, or `t_dev` with step_on_device -- the kernels subtract the one themselves; before the first record() and past the
         horizon nothing is written."""
-        if self.store is None or self.store.logp is None:
-            raise RuntimeError("record_policy() needs AgentTrajectories(..., obs_rows=(n_pred, n_prey), logp=(A_pred, A_prey))")
+        self._need_store("record_policy", logp=True)
         if self.step_on_device:
             self.store.record_logp(self.t_dev, logits, actions)
         elif self._t > 0:
@@ -319,8 +317,7 @@ class AgentTrajectories:
     def behaviour(self, species):
         """(logp[:n], entropy[:n] or None, dist[:n] or None) of one species, in the order of samples(): float32 [n], [n] and
         [n, A_s] (one read-back of the cursor).  NaN in logp / entropy where no policy was recorded for a sample."""
-        if self.store is None or self.store.logp is None:
-            raise RuntimeError("behaviour() needs AgentTrajectories(..., obs_rows=(n_pred, n_prey), logp=(A_pred, A_prey))")
+        self._need_store("behaviour", logp=True)
         st = self.store
         n = int(st.cursor[species].item())
         return (st.logp[species][:n], None if st.entropy is None else st.entropy[species][:n],
@@ -330,8 +327,7 @@ class AgentTrajectories:
         """The inverse of flat(): a [len,B,S] tensor with x_s[k] at the (t, b, r) of sample k of species s and `fill` everywhere else --
         what brings a critic's per-sample values into the layout gae() takes.  x_pred / x_prey: [n_s] tensors of one dtype in sample
         order (either may be None).  Plain torch index ops, one read-back of the cursor."""
-        if self.store is None:
-            raise RuntimeError("scatter() needs a store: AgentTrajectories(..., obs_rows=(n_pred, n_prey))")
+        self._need_store("scatter")
         given = [x for x in (x_pred, x_prey) if x is not None]
         if not given:
             raise ValueError("scatter() needs at least one of x_pred, x_prey")
@@ -351,8 +347,7 @@ class AgentTrajectories:
     def record_obs_torch(self, actions=None):
         """record(actions) of a trajectory with a store as torch ops: record_torch() plus ObservationStore.record_obs_torch() -- the
         same bytes; the host waits for the device (timing baseline, fallback)."""
-        if self.store is None:
-            raise RuntimeError("record_obs_torch() needs a store: AgentTrajectories(..., obs_rows=(n_pred, n_prey))")
+        self._need_store("record_obs_torch")
         t = self.t
         self.record_torch()
         self.store.record_obs_torch(t, actions)
@@ -363,8 +358,7 @@ class AgentTrajectories:
         observations [n,C,R,R], the flat index (t * B + b) * S + r of each as int64 -- `x.reshape(-1)[index]` picks a sample's element
         of any [len,B,S] tensor, which is what flat() does -- and the actions taken from them (None for a store without actions).
         Samples are ordered by step, then env, then row."""
-        if self.store is None:
-            raise RuntimeError("samples() needs a store: AgentTrajectories(..., obs_rows=(n_pred, n_prey))")
+        self._need_store("samples")
         st = self.store
         n = int(st.cursor[species].item())
         return n, st.obs[species][:n], st.sample[species][:n].long(), None if st.action is None else st.action[species][:n]
@@ -385,10 +379,7 @@ class AgentTrajectories:
         if t > 0:
             self.next_row[t - 1].copy_(next_row)
         self.next_row[t].fill_(-1)
-        n_pred = env.env_state[:, _abi.ENV_N_PRED_ROWS:_abi.ENV_N_PRED_ROWS + 1]
-        n_prey = env.env_state[:, _abi.ENV_N_PREY_ROWS:_abi.ENV_N_PREY_ROWS + 1]
-        cp = env.pred_capacity
-        used = torch.where(self._slot < cp, self._slot < n_pred, self._slot - cp < n_prey)
+        used = env.live_mask()
         self.in_use[t].copy_(used)
         self.reward[t].copy_(env.row_reward)
         self.terminated[t].copy_(((env.row_flags & _abi.ROW_DIED) != 0) & used)
@@ -485,8 +476,7 @@ class AgentTrajectories:
         [len,B,S] tensor of values, returns or advantages.  stats (None with stats=False): float64 [B,2,3], per env and species
         {count, sum A, sum A * A} of the unrounded advantages, for advantage_moments().  One read-back: the store's cursor (with
         step_on_device the step index comes with it).  An empty trajectory gives empty tensors without a launch."""
-        if self.store is None:
-            raise RuntimeError("targets() needs a store: AgentTrajectories(..., obs_rows=(n_pred, n_prey))")
+        self._need_store("targets")
         st, dev = self.store, self.reward.device
         if self.step_on_device:
             n_pred, n_prey, n = torch.cat((st.cursor[:2], self.t_dev.to(torch.int64))).tolist()   # (the one read-back)
@@ -510,8 +500,7 @@ class AgentTrajectories:
         """targets() as the composition it replaces -- scatter() into [len,B,S], returns_and_gae(), flat() per species, .float(): the
         same bits in adv and ret (timing baseline, fallback).  stats are index_add sums here: the same counts, the sums equal to
         targets()'s up to the order of the additions."""
-        if self.store is None:
-            raise RuntimeError("targets_torch() needs a store: AgentTrajectories(..., obs_rows=(n_pred, n_prey))")
+        self._need_store("targets_torch")
         n_steps, cursor = self.t, self.store.cursor.tolist()
         B, S = self.reward.shape[1:]
         v_pred, v_prey = (self._sample_values(v, cursor[s], s) for s, v in enumerate((v_pred, v_prey)))
@@ -596,7 +585,6 @@ class GraphedCollector:
         if logits is not None and act is None:
             raise ValueError("logits are what `act` fills: GraphedCollector(env, traj, act=..., logits=...)")
         self.env, self.traj = env, traj
-        dev = env.device
 
         def body():
             if act is not None:
@@ -608,16 +596,7 @@ class GraphedCollector:
             else:
                 env.step(random_actions=True, auto_reset=auto_reset)
                 traj.record()
-        # (one uncaptured pass on a side stream first: lazy allocations of the library and of the env must not fall into the capture)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            body()
+        self.graph = capture_graph(env.device, body)
 
     def replay(self, n: int = 1):
         for _ in range(n):

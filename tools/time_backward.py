@@ -12,35 +12,12 @@ started.  The kernel is also timed with its loads placed at the top of each step
 import argparse
 import os
 import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from timing import fmt, repeat_ms, run_children   # (tools/timing.py)
 
 SHAPES = [("default", {}, 32), ("default", {}, 128), ("p128q256", {"pred_capacity": 128, "prey_capacity": 256}, 32)]
 PEAK = 8.0e12   # bytes/s (MI355X HBM3E, spec)
-
-
-def time_ms(fn, reps, warmup):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b))
-    return out
-
-
-def fmt(ts):
-    return f"{statistics.median(ts):9.3f} ({min(ts):.3f}-{max(ts):.3f})"
 
 
 def child(args):
@@ -83,18 +60,18 @@ def child(args):
     print("| what | ms | bytes moved | of 8 TB/s |\n|---|---|---|---|")
     med = {}
     for name, fn, reps, nbytes in rows:
-        ts = time_ms(fn, reps, args.warmup)
+        ts = repeat_ms(fn, reps, args.warmup)
         med[name[:3]] = ts
         extra = f" {nbytes / 1e6:.0f} MB | {nbytes / (statistics.median(ts) * 1e-3) / PEAK:.3f} |" if nbytes else " | |"
-        print(f"| {name} | {fmt(ts)} |{extra}", flush=True)
+        print(f"| {name} | {fmt(ts, 3)} |{extra}", flush=True)
     # load placement: one step ahead (default) against the top of the step, alternating in one process
     ahead, top = [], []
     both = lambda e: (lambda: e.backward(*stored, gamma, lam, values=values))
     for _ in range(3):
-        ahead += time_ms(both(env), max(3, args.reps // 3), 1)
-        top += time_ms(both(env_np), max(3, args.reps // 3), 1)
-    print(f"| (e) through env.backward(), loads one step ahead | {fmt(ahead)} | | |")
-    print(f"| (e) through env.backward(), loads at the top of the step | {fmt(top)} | | |")
+        ahead += repeat_ms(both(env), max(3, args.reps // 3), 1)
+        top += repeat_ms(both(env_np), max(3, args.reps // 3), 1)
+    print(f"| (e) through env.backward(), loads one step ahead | {fmt(ahead, 3)} | | |")
+    print(f"| (e) through env.backward(), loads at the top of the step | {fmt(top, 3)} | | |")
     d, b = med["(d)"], med["(b)"]
     print(f"gae(): torch {statistics.median(b):.3f} ms -> kernel {statistics.median(d):.3f} ms = {statistics.median(b) / statistics.median(d):.1f}x "
           f"(spread: torch {max(b) - min(b):.3f}, kernel {max(d) - min(d):.3f} ms)", flush=True)
@@ -111,17 +88,8 @@ def main():
     args = ap.parse_args()
     if args.child is not None:
         return child(args)
-    for i in range(len(SHAPES)):
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", str(i), "--batch", str(args.batch), "--reps", str(args.reps),
-               "--reps-torch", str(args.reps_torch), "--warmup", str(args.warmup)]
-        try:
-            rc = subprocess.run(cmd, timeout=args.limit).returncode
-        except subprocess.TimeoutExpired:
-            rc = 124
-        if rc != 0:
-            print(f"shape {i} ended with status {rc}: nothing more is started", flush=True)
-            return rc
-    return 0
+    passed = ["--batch", str(args.batch), "--reps", str(args.reps), "--reps-torch", str(args.reps_torch), "--warmup", str(args.warmup)]
+    return run_children(__file__, len(SHAPES), passed, args.limit, lambda i: f"shape {i}")
 
 
 if __name__ == "__main__":

@@ -13,15 +13,11 @@ its default), alternating in one process, and without the stats and without the 
 import argparse
 import os
 import statistics
-import subprocess
 import sys
 import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from tools.time_backward import PEAK, SHAPES, fmt, time_ms   # noqa: E402  (the shapes and the clock of the ppg_backward record)
+from time_backward import PEAK, SHAPES   # (tools/time_backward.py: the shapes of the ppg_backward record)
+from timing import fmt, repeat_ms, run_children   # (tools/timing.py)
 
 # store rows per env-step (predators, prey): about twice what the default population has in use (15-17 rows per env-step); the
 # observations themselves are not what is timed, so the envs hold them as bfloat16 (10 GB of store at 128 steps of 4096 envs)
@@ -83,18 +79,18 @@ def child(args):
     print("| what | ms | bytes counted | of 8 TB/s |\n|---|---|---|---|")
     med = {}
     for label, fn, reps, nbytes in rows:
-        ts = time_ms(fn, reps, args.warmup)
+        ts = repeat_ms(fn, reps, args.warmup)
         med[label[:3]] = ts
         extra = f" {nbytes / 1e6:.0f} MB | {nbytes / (statistics.median(ts) * 1e-3) / PEAK:.3f} |" if nbytes else " | |"
-        print(f"| {label} | {fmt(ts)} |{extra}", flush=True)
+        print(f"| {label} | {fmt(ts, 3)} |{extra}", flush=True)
     # load placement: one step ahead (default) against the top of the step, alternating in one process
     ahead, top = [], []
     both = lambda e: (lambda: e.backward_samples(view, *stored, gamma, lam, values=v, stats=True))
     for _ in range(3):
-        ahead += time_ms(both(placed["1"]), max(3, args.reps // 3), 1)
-        top += time_ms(both(placed["0"]), max(3, args.reps // 3), 1)
-    print(f"| (c) through env.backward_samples(), loads one step ahead (PPG_BACKWARD_PREFETCH=1) | {fmt(ahead)} | | |")
-    print(f"| (c) through env.backward_samples(), loads at the top of the step (=0, the default) | {fmt(top)} | | |")
+        ahead += repeat_ms(both(placed["1"]), max(3, args.reps // 3), 1)
+        top += repeat_ms(both(placed["0"]), max(3, args.reps // 3), 1)
+    print(f"| (c) through env.backward_samples(), loads one step ahead (PPG_BACKWARD_PREFETCH=1) | {fmt(ahead, 3)} | | |")
+    print(f"| (c) through env.backward_samples(), loads at the top of the step (=0, the default) | {fmt(top, 3)} | | |")
     a, c = med["(a)"], med["(c)"]
     verdict = "ranges disjoint, the kernel's the lower" if max(c) < min(a) else "RANGES OVERLAP OR THE KERNEL IS NOT THE LOWER"
     print(f"targets(): torch composition {statistics.median(a):.3f} ms -> kernel {statistics.median(c):.3f} ms = "
@@ -112,17 +108,8 @@ def main():
     args = ap.parse_args()
     if args.child is not None:
         return child(args)
-    for i in range(len(SHAPES)):
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", str(i), "--batch", str(args.batch), "--reps", str(args.reps),
-               "--reps-torch", str(args.reps_torch), "--warmup", str(args.warmup)]
-        try:
-            rc = subprocess.run(cmd, timeout=args.limit).returncode
-        except subprocess.TimeoutExpired:
-            rc = 124
-        if rc != 0:
-            print(f"shape {i} ended with status {rc}: nothing more is started", flush=True)
-            return rc
-    return 0
+    passed = ["--batch", str(args.batch), "--reps", str(args.reps), "--reps-torch", str(args.reps_torch), "--warmup", str(args.warmup)]
+    return run_children(__file__, len(SHAPES), passed, args.limit, lambda i: f"shape {i}")
 
 
 if __name__ == "__main__":

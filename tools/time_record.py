@@ -16,26 +16,17 @@ per-step time.  Before any timing the bytes of record() are compared with record
 Each shape runs in a child process of its own under a time limit; after a child that fails or runs out of time nothing more is
 started."""
 import argparse
-import os
 import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from timing import alternate, fmt, run_children   # (tools/timing.py)
 
 SHAPES = [("default", {}), ("p128q256", {"pred_capacity": 128, "prey_capacity": 256})]
 NAMES = ("reward", "in_use", "terminated", "truncated", "next_row")
 
 
-def fmt(ts):
-    return f"{statistics.median(ts):7.1f} ({min(ts):.1f}-{max(ts):.1f})"
-
-
 def child(args):
     import torch
-    from predpreygrass_amd import _abi
     from predpreygrass_amd.batched import BatchedPredPreyGrass
     from predpreygrass_amd.config import config_env
     from predpreygrass_amd.trajectory import AgentTrajectories, GraphedCollector
@@ -77,8 +68,8 @@ def child(args):
     for k in NAMES:
         assert torch.equal(getattr(traj, k).view(torch.uint8), getattr(want, k).view(torch.uint8)), f"kernel != record_torch(): {k}"
     assert bool((traj.next_row >= 0).any()), "nothing linked"
-    n_pred = env.env_state[:, _abi.ENV_N_PRED_ROWS].double().mean().item()
-    n_prey = env.env_state[:, _abi.ENV_N_PREY_ROWS].double().mean().item()
+    live = env.live_mask()
+    n_pred, n_prey = live[:, :env.pred_capacity].sum().item() / B, live[:, env.pred_capacity:].sum().item() / B
     del twin, want
 
     dev_traj = AgentTrajectories(env, T, step_on_device=True)
@@ -110,23 +101,13 @@ def child(args):
     modes = [("(a) the step alone", block_a), ("(b) step + link()", block_b), ("(c) step + record_torch()", block_c),
              ("(d) step + record(), the kernel", block_d), ("(e) GraphedCollector.replay", block_e)]
     n = min(args.block, T)
-    times = {name: [] for name, _ in modes}
-    for rep in range(args.reps + 1):   # (the first round is the warm-up)
-        for name, fn in modes:
-            torch.cuda.synchronize()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn(n)
-            b.record()
-            b.synchronize()
-            if rep > 0:
-                times[name].append(a.elapsed_time(b) * 1000.0 / n)
+    times = alternate(modes, args.reps, n)
     print(f"### B = {B}, S = {S} ({SHAPES[args.child][0]}), horizon {T}: {n_pred:.1f} predator + {n_prey:.1f} prey rows per env after "
           f"{args.preroll} steps, kernel {env.step_kernel_name()}, plan {env.wave_plan()}; µs per step, launch to launch, {args.reps} blocks "
           f"of {n} steps each, median (min-max)", flush=True)
     print("| what | µs per step |\n|---|---|")
     for name, _ in modes:
-        print(f"| {name} | {fmt(times[name])} |", flush=True)
+        print(f"| {name} | {fmt(times[name], 1)} |", flush=True)
     med = {name[:3]: statistics.median(ts) for name, ts in times.items()}
     spread = {name[:3]: max(ts) - min(ts) for name, ts in times.items()}
     print(f"record_torch() costs {med['(c)'] - med['(a)']:.1f} µs per step, the kernel {med['(d)'] - med['(a)']:.1f}, link() alone "
@@ -146,17 +127,9 @@ def main():
     args = ap.parse_args()
     if args.child is not None:
         return child(args)
-    for i in range(len(SHAPES)):
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", str(i), "--batch", str(args.batch), "--horizon", str(args.horizon),
-               "--block", str(args.block), "--reps", str(args.reps), "--preroll", str(args.preroll)]
-        try:
-            rc = subprocess.run(cmd, timeout=args.limit).returncode
-        except subprocess.TimeoutExpired:
-            rc = 124
-        if rc != 0:
-            print(f"shape {i} ended with status {rc}: nothing more is started", flush=True)
-            return rc
-    return 0
+    passed = ["--batch", str(args.batch), "--horizon", str(args.horizon), "--block", str(args.block), "--reps", str(args.reps),
+              "--preroll", str(args.preroll)]
+    return run_children(__file__, len(SHAPES), passed, args.limit, lambda i: f"shape {i}")
 
 
 if __name__ == "__main__":

@@ -18,24 +18,14 @@ size.
 
 The measurement runs in a child process under a time limit."""
 import argparse
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-
-def fmt(ts):
-    return f"{statistics.median(ts):7.1f} ({min(ts):.1f}-{max(ts):.1f})"
+from timing import alternate, fmt, run_children   # (tools/timing.py)
 
 
 def child(args):
     import numpy as np
     import torch
-    from predpreygrass_amd import _abi
     from predpreygrass_amd.batched import BatchedPredPreyGrass
     from predpreygrass_amd.config import config_env
     from predpreygrass_amd.policy import FusedPolicy, PolicyNet
@@ -64,9 +54,8 @@ def child(args):
     for _ in range(args.preroll):   # to the population the policy settles at
         act()
         env.step(env.actions, auto_reset=True)
-    es = env.env_state
-    n_pred = es[:, _abi.ENV_N_PRED_ROWS].clamp(0, env.pred_capacity).sum().item()
-    n_prey = es[:, _abi.ENV_N_PREY_ROWS].clamp(0, env.prey_capacity).sum().item()
+    live = env.live_mask()
+    n_pred, n_prey = live[:, :env.pred_capacity].sum().item(), live[:, env.pred_capacity:].sum().item()
     rows = (int(T * n_pred * 1.5) + B, int(T * n_prey * 1.5) + B)
     traj = AgentTrajectories(env, T, obs_rows=rows, logp=A)
     other = ObservationStore(env, T, rows, logp=A)
@@ -105,29 +94,19 @@ def child(args):
     modes = [("(a) act + step + record + record_obs", block(lambda t: None)),
              ("(b) act + record_logp + step + record + record_obs", block(lambda t: traj.store.record_logp(t, bufs))),
              ("(c) act + record_logp_torch + step + record + record_obs", block(lambda t: traj.store.record_logp_torch(t, bufs)))]
-    times = {name: [] for name, _ in modes}
-    stored = dropped = 0
-    for rep in range(args.reps + 1):   # (the first round is the warm-up)
-        for name, fn in modes:
-            torch.cuda.synchronize()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn(T)
-            b.record()
-            b.synchronize()
-            if rep > 0:
-                times[name].append(a.elapsed_time(b) * 1000.0 / T)
-            (sp, dp), (sq, dq) = traj.store.counts()
-            stored, dropped = (sp / T, sq / T), dp + dq
+    counts = []
+    times = alternate(modes, args.reps, T, after={name: lambda: counts.append(traj.store.counts()) for name, _ in modes})
+    (sp, dp), (sq, dq) = counts[-1]
+    stored, dropped = (sp / T, sq / T), dp + dq
     ta, tb, tc = (times[name] for name, _ in modes)
     print(f"### B = {B}, S = {env.S}, {A[0]} / {A[1]} actions, kernel {env.step_kernel_name()}; {stored[0]:.0f} predator + {stored[1]:.0f} prey "
           f"rows stored per step, {dropped} dropped; µs per step, launch to launch, {args.reps} rounds of blocks of {T} steps, median (min-max)", flush=True)
     print("| what | µs per step | every round |\n|---|---|---|")
     for name, _ in modes:
-        print(f"| {name} | {fmt(times[name])} | {' '.join(f'{x:.1f}' for x in times[name])} |", flush=True)
+        print(f"| {name} | {fmt(times[name], 1)} | {' '.join(f'{x:.1f}' for x in times[name])} |", flush=True)
     kernel, torch_ops = [y - x for x, y in zip(ta, tb)], [y - x for x, y in zip(ta, tc)]
-    print(f"| (b) - (a): record_logp() | {fmt(kernel)} | {' '.join(f'{x:.1f}' for x in kernel)} |")
-    print(f"| (c) - (a): record_logp_torch() | {fmt(torch_ops)} | {' '.join(f'{x:.1f}' for x in torch_ops)} |", flush=True)
+    print(f"| (b) - (a): record_logp() | {fmt(kernel, 1)} | {' '.join(f'{x:.1f}' for x in kernel)} |")
+    print(f"| (c) - (a): record_logp_torch() | {fmt(torch_ops, 1)} | {' '.join(f'{x:.1f}' for x in torch_ops)} |", flush=True)
     cheaper = all(k < t for k, t in zip(kernel, torch_ops))
     print(f"record_logp() is {'cheaper than' if cheaper else 'NOT cheaper than'} record_logp_torch() in every round", flush=True)
     fused.close()
@@ -141,19 +120,12 @@ def main():
     ap.add_argument("--reps", type=int, default=7, help="timed rounds")
     ap.add_argument("--preroll", type=int, default=300, help="steps before anything is timed")
     ap.add_argument("--limit", type=int, default=300, help="seconds the child process may take")
-    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
-    if args.child:
+    if args.child is not None:
         return child(args)
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--batch", str(args.batch), "--block", str(args.block),
-           "--reps", str(args.reps), "--preroll", str(args.preroll)]
-    try:
-        rc = subprocess.run(cmd, timeout=args.limit).returncode
-    except subprocess.TimeoutExpired:
-        rc = 124
-    if rc != 0:
-        print(f"the measurement ended with status {rc}", flush=True)
-    return rc
+    passed = ["--batch", str(args.batch), "--block", str(args.block), "--reps", str(args.reps), "--preroll", str(args.preroll)]
+    return run_children(__file__, 1, passed, args.limit, lambda i: "the measurement")
 
 
 if __name__ == "__main__":

@@ -19,20 +19,12 @@ Each dtype runs in a child process of its own under a time limit; after a child 
 started."""
 import argparse
 import ctypes as C
-import os
 import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from timing import alternate, fmt, run_children   # (tools/timing.py)
 
 DTYPES = ["bfloat16", "float64"]
-
-
-def fmt(ts):
-    return f"{statistics.median(ts):7.1f} ({min(ts):.1f}-{max(ts):.1f})"
 
 
 def child(args):
@@ -51,14 +43,11 @@ def child(args):
     def step():
         env.step(random_actions=True, auto_reset=True)
 
-    def rows_in_use():
-        es = env.env_state
-        return (es[:, _abi.ENV_N_PRED_ROWS].clamp(0, env.pred_capacity).sum().item(), es[:, _abi.ENV_N_PREY_ROWS].clamp(0, env.prey_capacity).sum().item())
-
     env.reset()
     for _ in range(args.preroll):   # to a stationary population
         step()
-    n_pred, n_prey = rows_in_use()
+    live = env.live_mask()
+    n_pred, n_prey = live[:, :env.pred_capacity].sum().item(), live[:, env.pred_capacity:].sum().item()
     # stores for one block of steps at the stationary population, with a quarter to spare (what does not fit is dropped, and reported)
     rows = (int(T * n_pred * 1.25) + B, int(T * n_prey * 1.25) + B)
     traj = AgentTrajectories(env, T)
@@ -110,21 +99,10 @@ def child(args):
 
     modes = [("(a) step + record()", block_a), ("(b) step + record() + record_obs()", block_b),
              ("(c) step + record() + record_obs_torch()", block_c), ("(d) step + ppg_pack", block_d)]
-    times = {name: [] for name, _ in modes}
-    stored = dropped = 0
-    for rep in range(args.reps + 1):   # (the first round is the warm-up)
-        for name, fn in modes:
-            torch.cuda.synchronize()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn(T)
-            b.record()
-            b.synchronize()
-            if rep > 0:
-                times[name].append(a.elapsed_time(b) * 1000.0 / T)
-            if fn is block_b:
-                (sp, dp), (sq, dq) = store.counts()
-                stored, dropped = (sp / T, sq / T), dp + dq
+    counts = []
+    times = alternate(modes, args.reps, T, after={modes[1][0]: lambda: counts.append(store.counts())})
+    (sp, dp), (sq, dq) = counts[-1]
+    stored, dropped = (sp / T, sq / T), dp + dq
     header = _abi.PpgPackHeader.from_buffer_copy(image[:64].cpu().numpy().tobytes())
     per_step = sum(stored[s] * (blk[s] * 2 * elem + 5) for s in (0, 1)) + B * S * 4
     med = {name[:3]: statistics.median(ts) for name, ts in times.items()}
@@ -134,7 +112,7 @@ def child(args):
           f"ppg_pack overflow {header.overflow}; µs per step, launch to launch, {args.reps} blocks of {T} steps each, median (min-max)", flush=True)
     print("| what | µs per step |\n|---|---|")
     for name, _ in modes:
-        print(f"| {name} | {fmt(times[name])} |", flush=True)
+        print(f"| {name} | {fmt(times[name], 1)} |", flush=True)
     cost = med["(b)"] - med["(a)"]
     print(f"record_obs() costs {cost:.1f} µs per step, record_obs_torch() {med['(c)'] - med['(a)']:.1f}, ppg_pack {med['(d)'] - med['(a)']:.1f} "
           f"(spreads: (a) {spread['(a)']:.1f}, (b) {spread['(b)']:.1f}, (c) {spread['(c)']:.1f}, (d) {spread['(d)']:.1f}); "
@@ -152,17 +130,8 @@ def main():
     args = ap.parse_args()
     if args.child is not None:
         return child(args)
-    for i in range(len(DTYPES)):
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", str(i), "--batch", str(args.batch), "--block", str(args.block),
-               "--reps", str(args.reps), "--preroll", str(args.preroll)]
-        try:
-            rc = subprocess.run(cmd, timeout=args.limit).returncode
-        except subprocess.TimeoutExpired:
-            rc = 124
-        if rc != 0:
-            print(f"{DTYPES[i]} ended with status {rc}: nothing more is started", flush=True)
-            return rc
-    return 0
+    passed = ["--batch", str(args.batch), "--block", str(args.block), "--reps", str(args.reps), "--preroll", str(args.preroll)]
+    return run_children(__file__, len(DTYPES), passed, args.limit, lambda i: DTYPES[i])
 
 
 if __name__ == "__main__":
