@@ -359,17 +359,6 @@ struct ConvW {
     }
 };
 
-#ifdef PPG_EXPERIMENTS   // ablation builds (-DPPG_ABLATE=bits, timing only): 64 no ReLU / pack / stores, 128 the convolutions' MFMAs become one
-// v_add per fragment, 256 no LDS fragment reads, 512 no position arithmetic
-#ifndef PPG_ABLATE
-#define PPG_ABLATE 0
-#endif
-#define PPG_MFMA(a, b, c) ((PPG_ABLATE & 128) ? ppg_fake_mfma(a, b, c) : __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0))
-__device__ __forceinline__ f32x16 ppg_fake_mfma(bf16x8 a, bf16x8 b, f32x16 c) { c[0] += (float)a[0] + (float)b[0]; return c; }
-#else
-#define PPG_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-#endif
-
 // One convolution layer over the `ns` samples of a sub-group, this wavefront's share of the 32-position tiles.
 //   COUT_BLOCKS  channel blocks written: 2 (conv1), 4 (conv2), 8 (conv3)
 //   TO_GLOBAL    conv3: the result goes to the scratch slot X[sample][position][64] instead of an LDS image
@@ -391,19 +380,9 @@ __device__ __forceinline__ void conv_layer(const KP &K, const ConvW<CBIN, MT> &W
         const int n = 32 * nt + col;
         const bool valid = n < n_pos;
         const int nn = valid ? n : 0;
-#ifdef PPG_EXPERIMENTS
-        int s, p, pidx;
-        if (PPG_ABLATE & 512) { s = 0; p = col; pidx = K.Wp + 1 + col; }   // ablation: no position arithmetic
-        else {
-            s = div_small(nn, K.magic_P); p = nn - __mul24(s, K.P);
-            const int y = div_small(p, K.magic_R), x = p - __mul24(y, K.IW);
-            pidx = __mul24(y + 1, K.Wp) + (x + 1);
-        }
-#else
         const int s = div_small(nn, K.magic_P), p = nn - __mul24(s, K.P);
         const int y = div_small(p, K.magic_R), x = p - __mul24(y, K.IW);
         const int pidx = __mul24(y + 1, K.Wp) + (x + 1);
-#endif
         const __bf16 *base = in + __mul24(s, sample_stride) + pidx * 8;
         f32x16 acc[MT];
 #pragma unroll
@@ -418,9 +397,6 @@ __device__ __forceinline__ void conv_layer(const KP &K, const ConvW<CBIN, MT> &W
                 v = zero8();
                 if (h == HB) { v[0] = (__bf16)1.0f; v[1] = (__bf16)1.0f; }
             } else {
-#ifdef PPG_EXPERIMENTS
-                if (PPG_ABLATE & 256) v = zero8(); else   // ablation: no LDS fragment reads
-#endif
                 v = *(const bf16x8 *)(base + W.offset(K, ks, d23));
                 if (ks == KSB && h == HB) { v = zero8(); v[0] = (__bf16)1.0f; v[1] = (__bf16)1.0f; }
             }
@@ -439,7 +415,7 @@ __device__ __forceinline__ void conv_layer(const KP &K, const ConvW<CBIN, MT> &W
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[mt] = PPG_MFMA(W.a[mt][ks], b[ks], acc[mt]);
+                for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W.a[mt][ks], b[ks], acc[mt], 0, 0, 0);
         } else {
             // conv3 (19 k-steps): the fragments come in batches of BATCH, batch n + 1 requested before the MFMAs of batch n -- two
             // batches of registers instead of 76, which is what lets the weights of all three layers stay in registers
@@ -459,18 +435,12 @@ __device__ __forceinline__ void conv_layer(const KP &K, const ConvW<CBIN, MT> &W
                     if (nb * BATCH + i < KS) {
 #pragma unroll
                         for (int mt = 0; mt < MT; ++mt)
-                            acc[mt] = PPG_MFMA(W.a[mt][nb * BATCH + i], b[nb & 1][i], acc[mt]);
+                            acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W.a[mt][nb * BATCH + i], b[nb & 1][i], acc[mt], 0, 0, 0);
                     }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
         if (!valid || (TO_GLOBAL && (K.debug_skip & 32))) continue;
-#ifdef PPG_EXPERIMENTS
-        if (PPG_ABLATE & 64) {   // ablation: no ReLU / pack / stores (one value stored so that the MFMAs stay)
-            if (acc[0][0] == 123.0f) *(float *)(img) = acc[0][0];
-            continue;
-        }
-#endif
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -1169,14 +1139,11 @@ int ppg_policy_create(int32_t device, int32_t obs_range, int32_t n_actions, cons
 
 int ppg_policy_destroy(ppg_policy *p);
 
-#ifndef PPG_POLICY_PIPE
-#define PPG_POLICY_PIPE 1   // (0: A/B builds without the two-role pipeline)
-#endif
 // diagnostic switch: environment variable PPG_POLICY_PIPE=0 at creation time sends a network the pipeline would take to the one-role
 // direct-head kernels instead (tests compare the two bit for bit)
 static bool ppg_pipe_enabled() {
     const char *e = getenv("PPG_POLICY_PIPE");
-    return PPG_POLICY_PIPE && !(e && e[0] == '0' && e[1] == 0);
+    return !(e && e[0] == '0' && e[1] == 0);
 }
 // The pipeline's SLOT TABLE (ppg_policy_direct.h: dconv_cells): the ST * P positions of a sub-group in an order in which slot n's cell of
 // the padded image -- 16-byte cell number sample * stride_cells + (y + 1) * Wp + x + 1 -- is congruent to n modulo 16.  A 32-slot MFMA
@@ -1361,16 +1328,15 @@ static int ppg_policy_layout_of(const ppg_policy_spec &sp, bool allow_pipe, ppg_
         return PPG_OK;
     }
     const int fixed = ppgpol::TILE * 16 + K.head_mt * 4096 + 4096 + tail_slack;   // table, partial logits, dconv's dummy slots
-    const bool w1 = PPG_DIRECT_W1;   // one workgroup per CU with all of its LDS (ppg_policy_direct.h)
-    int st_max = ((w1 ? 160 : 80) * 1024 - fixed) / (K.sample_stride * 2);
+    int st_max = (160 * 1024 - fixed) / (K.sample_stride * 2);   // one workgroup per CU with all of its LDS (ppg_policy_direct.h)
     if (st_max > 16) st_max = 16;                // (the head's 16 sample columns)
-    while (st_max > 1 && st_max * P > (w1 ? 512 : 256)) --st_max;   // a thread stages at most two / one positions
+    while (st_max > 1 && st_max * P > 512) --st_max;   // a thread stages at most two positions
     if (st_max < 1)
         return ppg_policy_fail(nullptr, PPG_EINVAL, "a %d x %d image with %d convolutions needs %d bytes of LDS per sample: too large", IH, IW, sp.n_conv, K.sample_stride * 2);
     const int st = ppg_subgroup_samples(st_max, P);
     K.ST = st;
     K.range_tile = st * (ppgpol::TILE / st);   // whole sub-groups per tile
-    L.family = sp.n_conv > 3 ? 2 : 1; L.wgs_per_cu = w1 ? 1 : 2; L.lds_bytes = fixed + st * K.sample_stride * 2;
+    L.family = sp.n_conv > 3 ? 2 : 1; L.wgs_per_cu = 1; L.lds_bytes = fixed + st * K.sample_stride * 2;
     return PPG_OK;
 }
 
@@ -1530,11 +1496,8 @@ int ppg_policy_create_spec(int32_t device, const ppg_policy_spec *spec, ppg_poli
     } else if (L.family == 0) {
         const size_t xg_bytes = (size_t)p->grid * ppgpol::TILE * K1 * 2;
         // the scratch slots: 512 concurrent sequential streams, written by conv3 and read back by FC1 -- on spread physical pages like the
-        // env's observation tensors where the virtual-memory calls work (-DPPG_POLICY_XG_SPREAD=0: A/B builds)
-#ifndef PPG_POLICY_XG_SPREAD
-#define PPG_POLICY_XG_SPREAD 16
-#endif
-        const int xg_spread = PPG_POLICY_XG_SPREAD;
+        // env's observation tensors where the virtual-memory calls work
+        constexpr int xg_spread = 16;
         void *xg_ptr = nullptr;
         p->xg_is_spread = xg_spread > 1 && ppg_alloc_spread(device, (uint64_t)xg_bytes, xg_spread, 0x5850u + (uint64_t)R, &xg_ptr) == PPG_OK;
         if (p->xg_is_spread) p->xg = (__bf16 *)xg_ptr;
@@ -1635,6 +1598,10 @@ static int ppg_policy_ensure_plan(ppg_policy *p, int total, int cap) {
     return PPG_OK;
 }
 
+// ---- the diagnostic builds' part of the launch path ----
+// ppg_policy_run and ppg_policy_run_fused call ppg_policy_diag_before() ahead of their launches and ppg_policy_diag_after() behind the
+// hipGetLastError() that follows them: arm, launch, hipGetLastError, check or write.  The product build's versions are empty.
+#if defined(PPG_PIPE_DEBUG) || defined(PPG_EXPERIMENTS) || defined(PPG_DIRECT_PROFILE)
 #ifdef PPG_PIPE_DEBUG
 // diagnostic build: status words the pipeline kernels' bounded waits report into; checked (with a device synchronisation) after every
 // launch.  PPG_PIPE_DEBUG_INJECT=1 (tests): pretend a report, to exercise the path that turns it into an error.
@@ -1698,6 +1665,54 @@ static ppg_policy_dump g_ppg_direct_profile[3] = {{"PPG_DIRECT_PROFILE_FILE", "P
                                                   {"PPG_DIRECT_PROFILE_FILE", "PPG_DIRECT_PROFILE_RUN"}};
 // [workgroup][wavefront][16] (the pipeline kernels have eight wavefronts, the others use the first half)
 static size_t ppg_direct_profile_bytes(const ppg_policy *p) { return (size_t)p->grid * 8 * 16 * 8; }
+#endif
+#ifdef PPG_EXPERIMENTS
+static size_t ppg_timeline_bytes(const ppgpol::PolParams &K, int total) { return (((size_t)total * K.cap + 31) / 32 + 1) * 512; }   // [tile][64] stamps
+#endif
+// launch: 0 the predators' launch, 1 the prey's, 2 the fused launch of both (K: the prey's block, K_also: the predators', L: none)
+static int ppg_policy_diag_before(ppg_policy *p, int launch, int total, ppgpol::PolParams &K, ppgpol::PolParams *K_also, ppgpol::PlanParams *L) {
+    int rc = PPG_OK;
+#ifdef PPG_EXPERIMENTS
+    if (launch < 2) {
+        if (const char *f = getenv(launch ? "PPG_POLICY_TILE_PREY" : "PPG_POLICY_TILE_PRED")) {
+            const int v = atoi(f);
+            if (v == 32 || v == 64 || v == 96 || v == 128) L->force_ts = v;
+        }
+        if ((rc = ppg_policy_dump_arm(p, g_ppg_timeline[launch], ppg_timeline_bytes(K, total), (void **)&K.timeline)) != PPG_OK) return rc;
+    }
+#endif
+#ifdef PPG_DIRECT_PROFILE   // (the FC chain's kernels write no profile: K.xg is their scratch)
+    if (p->direct) {
+        if ((rc = ppg_policy_dump_arm(p, g_ppg_direct_profile[launch], ppg_direct_profile_bytes(p), (void **)&K.xg)) != PPG_OK) return rc;
+        if (K_also) K_also->xg = K.xg;
+    }
+#endif
+#ifdef PPG_PIPE_DEBUG
+    if (p->direct && (rc = ppg_pipe_debug_arm(p)) != PPG_OK) return rc;
+#endif
+    (void)launch; (void)total; (void)K; (void)K_also; (void)L;
+    return rc;
+}
+static int ppg_policy_diag_after(ppg_policy *p, int launch, int total, const ppgpol::PolParams &K) {
+    int rc = PPG_OK;
+#ifdef PPG_PIPE_DEBUG
+    if (p->direct && (rc = ppg_pipe_debug_check(p)) != PPG_OK) return rc;
+#endif
+#ifdef PPG_DIRECT_PROFILE
+    static const char *const suffix[3] = {"pred", "prey", "fused"};
+    if (p->direct && g_ppg_direct_profile[launch].armed)
+        if ((rc = ppg_policy_dump_write(p, g_ppg_direct_profile[launch], ppg_direct_profile_bytes(p), suffix[launch])) != PPG_OK) return rc;
+#endif
+#ifdef PPG_EXPERIMENTS
+    for (int sp = 0; sp < 2 && launch == 0 && g_ppg_timeline[0].armed; ++sp)   // (the predators' launch is the second of a step: it writes both species' stamps)
+        if ((rc = ppg_policy_dump_write(p, g_ppg_timeline[sp], ppg_timeline_bytes(K, total), sp ? "prey" : "pred")) != PPG_OK) return rc;
+#endif
+    (void)launch; (void)total; (void)K;
+    return rc;
+}
+#else
+static inline int ppg_policy_diag_before(ppg_policy *, int, int, ppgpol::PolParams &, ppgpol::PolParams *, ppgpol::PlanParams *) { return PPG_OK; }
+static inline int ppg_policy_diag_after(ppg_policy *, int, int, const ppgpol::PolParams &) { return PPG_OK; }
 #endif
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the process-global kernel symbol, not of a policy: two live policies that
@@ -1777,14 +1792,7 @@ static int ppg_policy_run(ppg_policy *p, int species, ppg_handle *const *handles
     L.slots = p->grid;
     L.range_tile = p->direct ? K.range_tile : 0;
     L.range_st = K.ST;
-#ifdef PPG_EXPERIMENTS
-    if (const char *f = getenv(species ? "PPG_POLICY_TILE_PREY" : "PPG_POLICY_TILE_PRED")) {
-        const int v = atoi(f);
-        if (v == 32 || v == 64 || v == 96 || v == 128) L.force_ts = v;
-    }
-    const size_t tl_bytes = (((size_t)total * K.cap + 31) / 32 + 1) * 512;   // [tile][64] stamps
-    if ((rc = ppg_policy_dump_arm(p, g_ppg_timeline[species], tl_bytes, (void **)&K.timeline)) != PPG_OK) return rc;
-#endif
+    if ((rc = ppg_policy_diag_before(p, species, total, K, nullptr, &L)) != PPG_OK) return rc;
     if (also_plan_for) {   // the other species' plan in the same launch: same envs, its row-count word, its buffers, its grid
         ppg_policy *o = also_plan_for;
         rc = ppg_policy_ensure_plan(o, total, species ? h0->base.cap_pred : h0->base.cap_prey);
@@ -1806,9 +1814,6 @@ static int ppg_policy_run(ppg_policy *p, int species, ppg_handle *const *handles
                               {ppgpol::ppg_policy_forward_hwc8_f64, ppgpol::ppg_policy_forward_hwc8_f32, ppgpol::ppg_policy_forward_hwc8_bf16},
                               {ppgpol::ppg_policy_forward_hwc16_f64, ppgpol::ppg_policy_forward_hwc16_f32, ppgpol::ppg_policy_forward_hwc16_bf16}};
     const int dt = K.obs_f32 == 2 ? 2 : K.obs_f32 ? 1 : 0;
-#ifdef PPG_DIRECT_PROFILE   // (the FC chain's kernels write no profile: K.xg is their scratch)
-    if (p->direct && (rc = ppg_policy_dump_arm(p, g_ppg_direct_profile[species], ppg_direct_profile_bytes(p), (void **)&K.xg)) != PPG_OK) return rc;
-#endif
     if (p->direct) {
         const fwd_fn dir[4][3] = {{ppgpol::ppg_policy_direct8_f64, ppgpol::ppg_policy_direct8_f32, ppgpol::ppg_policy_direct8_bf16},
                                   {ppgpol::ppg_policy_direct16_f64, ppgpol::ppg_policy_direct16_f32, ppgpol::ppg_policy_direct16_bf16},
@@ -1818,29 +1823,14 @@ static int ppg_policy_run(ppg_policy *p, int species, ppg_handle *const *handles
                                    {ppgpol::ppg_policy_pipe16_f64, ppgpol::ppg_policy_pipe16_f32, ppgpol::ppg_policy_pipe16_bf16}};
         const fwd_fn fn = p->pipe ? pipe[p->nch16 ? 1 : 0][dt] : dir[(p->direct == 2 ? 2 : 0) + (p->nch16 ? 1 : 0)][dt];
         if ((rc = ppg_policy_reserve_lds(p, (const void *)fn, p->lds_bytes)) != PPG_OK) return rc;
-#ifdef PPG_PIPE_DEBUG
-        if ((rc = ppg_pipe_debug_arm(p)) != PPG_OK) return rc;
-#endif
         hipLaunchKernelGGL(fn, dim3((unsigned)p->grid), dim3(p->pipe ? 512 : 256), (size_t)p->lds_bytes, (hipStream_t)stream, K);
-#ifdef PPG_PIPE_DEBUG
-        PPG_POL_TRY(p, hipGetLastError());
-        if ((rc = ppg_pipe_debug_check(p)) != PPG_OK) return rc;
-#endif
     } else {
         const int variant = p->layout == PPG_POLICY_LAYOUT_HWC ? (p->cin > 8 ? 2 : 1) : 0;
         if ((rc = ppg_policy_reserve_lds(p, (const void *)fwd[variant][dt], p->lds_bytes)) != PPG_OK) return rc;
         hipLaunchKernelGGL(fwd[variant][dt], dim3((unsigned)p->grid), dim3(256), (size_t)p->lds_bytes, (hipStream_t)stream, K);
     }
     PPG_POL_TRY(p, hipGetLastError());
-#ifdef PPG_DIRECT_PROFILE
-    if (p->direct && g_ppg_direct_profile[species].armed)
-        if ((rc = ppg_policy_dump_write(p, g_ppg_direct_profile[species], ppg_direct_profile_bytes(p), species ? "prey" : "pred")) != PPG_OK) return rc;
-#endif
-#ifdef PPG_EXPERIMENTS
-    for (int sp = 0; sp < 2 && species == 0 && g_ppg_timeline[0].armed; ++sp)   // (the predators' launch is the second of a step: it writes both species' stamps)
-        if ((rc = ppg_policy_dump_write(p, g_ppg_timeline[sp], tl_bytes, sp ? "prey" : "pred")) != PPG_OK) return rc;
-#endif
-    return PPG_OK;
+    return ppg_policy_diag_after(p, species, total, K);
 }
 
 // diagnostic switch: environment variable PPG_POLICY_FUSED=0 sends a call with both species' pipeline policies through the two
@@ -1885,23 +1875,11 @@ static int ppg_policy_run_fused(ppg_policy *pred, ppg_policy *prey, ppg_handle *
          {ppgpol::ppg_policy_pipe2_16_16_f64, ppgpol::ppg_policy_pipe2_16_16_f32, ppgpol::ppg_policy_pipe2_16_16_bf16}}};
     const int dt = K2.q.obs_f32 == 2 ? 2 : K2.q.obs_f32 ? 1 : 0;
     const fused_fn f = fn[prey->nch16 ? 1 : 0][pred->nch16 ? 1 : 0][dt];
-#ifdef PPG_DIRECT_PROFILE
-    if ((rc = ppg_policy_dump_arm(prey, g_ppg_direct_profile[2], ppg_direct_profile_bytes(prey), (void **)&K2.q.xg)) != PPG_OK) return rc;
-    K2.p.xg = K2.q.xg;
-#endif
     if ((rc = ppg_policy_reserve_lds(prey, (const void *)f, lds)) != PPG_OK) return ppg_policy_mirror(prey, rc);
-#ifdef PPG_PIPE_DEBUG
-    if ((rc = ppg_pipe_debug_arm(prey)) != PPG_OK) return ppg_policy_mirror(prey, rc);
-#endif
+    if ((rc = ppg_policy_diag_before(prey, 2, total_q, K2.q, &K2.p, nullptr)) != PPG_OK) return ppg_policy_mirror(prey, rc);
     hipLaunchKernelGGL(f, dim3((unsigned)prey->grid), dim3(512), (size_t)lds, (hipStream_t)stream, K2);
     PPG_POL_TRY(prey, hipGetLastError());
-#ifdef PPG_PIPE_DEBUG
-    if ((rc = ppg_pipe_debug_check(prey)) != PPG_OK) return ppg_policy_mirror(prey, rc);
-#endif
-#ifdef PPG_DIRECT_PROFILE
-    if (g_ppg_direct_profile[2].armed && (rc = ppg_policy_dump_write(prey, g_ppg_direct_profile[2], ppg_direct_profile_bytes(prey), "fused")) != PPG_OK) return rc;
-#endif
-    return PPG_OK;
+    return ppg_policy_mirror(prey, ppg_policy_diag_after(prey, 2, total_q, K2.q));
 }
 
 int ppg_policy_act(ppg_policy *pred, ppg_policy *prey, ppg_handle *const *handles, int32_t n, int8_t *const *actions,

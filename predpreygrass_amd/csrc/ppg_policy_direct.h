@@ -30,32 +30,23 @@ namespace ppgpol {
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-// timing-only ablation builds (tools/gpu_direct_ablate.sh; never defined in the product -- the results are then meaningless):
-// 1 no head k-loop, 2 no action selection, 4 no conv3, 8 no conv1 / conv2, 16 no observation staging, 32 no LDS fragment reads in the
-// convolutions, 64 no convolution epilogues
-#ifndef PPG_DIRECT_ABLATE
-#define PPG_DIRECT_ABLATE 0
-#endif
+// The direct-head kernels run ONE workgroup per CU (one wavefront per SIMD: 512 registers -- every weight of the network and the
+// head's fragments resident, both of conv3's row tiles in one wavefront, 160 KB of LDS = twice the samples per sub-group).  Two
+// workgroups per CU with 256 registers each (conv3's row tiles split over wavefront pairs, the head's fragments from L2 six at a time)
+// were the first version: profiles/r04/b_policy_direct_phase_profile_2wg_per_cu_first_version.txt, ..._1wg_per_cu.txt.  Where the time
+// goes, from timing-only builds with one phase removed: profiles/r04/b_policy_direct_ablations_first_version.txt,
+// b_policy_direct_conv_ablations.txt.
+constexpr int DIRECT_B12 = 0;   // fragment reads per batch in conv1 / conv2 (0 = all of a tile's at once)
+constexpr int DIRECT_B3 = 5;    // ... in conv3 (the resident-weight kernels; the deep ones: 3)
 // -DPPG_DIRECT_PROFILE (tools/gpu_direct_profile.sh): cycles per phase, summed per wavefront over the launch, into K.xg (unused by the
 // direct path) as [workgroup][wavefront][16] -- 0 tile set-up, 1 conv1, 2 its barrier, 3 conv2, 4 barrier, 5 conv3 (+ deeper), 6 barrier,
 // 7 partial sums to LDS, 8 barrier, 9 logits, 10 staging, 11 requests of the rows two sub-groups ahead, 12 head, 15 sub-groups
-// PPG_DIRECT_W1 (default 1): the direct-head kernels run ONE workgroup per CU (one wavefront per SIMD: 512 registers --
-// every weight of the network and the head's fragments resident, both of conv3's row tiles in one wavefront, 160 KB of LDS = twice the
-// samples per sub-group); 0 = two workgroups per CU with 256 registers each (conv3's row tiles split over wavefront pairs, the head's
-// fragments from L2 six at a time) -- the A/B build
-#ifndef PPG_DIRECT_W1
-#define PPG_DIRECT_W1 1
-#endif
-#ifndef PPG_DIRECT_B12
-#define PPG_DIRECT_B12 0
-#endif
-#ifndef PPG_DIRECT_B3
-#define PPG_DIRECT_B3 5
-#endif
 #ifdef PPG_DIRECT_PROFILE
 #define PPG_DP(i) do { const long long now_ = (long long)clock64(); dp_acc[i] += now_ - dp_prev; dp_prev = now_; } while (0)
+#define PPG_DP_COUNT(i) do { dp_acc[i] += 1; } while (0)
 #else
 #define PPG_DP(i) do { } while (0)
+#define PPG_DP_COUNT(i) do { } while (0)
 #endif
 
 // partial logits in LDS: [wavefront][action tile (head_mt of them)][action row][sample column] floats = head_mt * 4 KB
@@ -89,7 +80,7 @@ __device__ __forceinline__ void dconv_cells(const KP &K, int sample_stride, int 
 //                      [position][flat_c channels] (the head's input)
 //   dummy              element index (from img) of 16 bytes of LDS that belong to this lane alone: stores of lanes without a position
 //                      (the last tile's tail) or without a real channel block (conv1's upper half) go there -- no branch in the epilogue
-// ONE wavefront per SIMD runs this (PPG_DIRECT_W1), so nothing hides a stall but the code itself: the loop is software-pipelined by
+// ONE wavefront per SIMD runs this, so nothing hides a stall but the code itself: the loop is software-pipelined by
 // hand -- the epilogue of tile t (accumulators -> ReLU -> bf16 -> LDS) sits between the first fragment reads of tile t + 1 and its first
 // MFMA, where it covers the LDS latency, and the positions of tile t + 1 are computed behind the MFMAs of tile t.
 struct TileCtx { int in_base, out_base, swz; bool valid; };
@@ -111,10 +102,10 @@ __device__ __forceinline__ int f_koff(const KP &K, int k, int kq) {   // element
 // pre: nullptr, or this lane's two precomputed words per tile of this wavefront (tile t = nt_first + t nt_step, t < 2; ppg_policy_pipe.h,
 // where a wavefront's tiles are the same positions in every sub-group): pre[2 t] = sample base + 8 x padded position (the element of its
 // cell in channel block 0 of area 0), pre[2 t + 1] = (sample base + 64 x position) | (position & 7) -- dconv_cells() below.
-// DEPTH: batches of fragment reads in flight ahead of the batch the MFMAs consume (1: the read of batch n + 1 is issued before the MFMAs of
-// batch n -- with one-fragment batches the next fragment has 64 cycles of MFMA to arrive, less than an LDS round trip under load: the
-// convolution then runs at the LDS latency, not at the matrix pipe's pace; 2-3: a rolling window, still ONE read issued at a time).
-template <int CBIN, int MT, int BATCH, bool SWP = true, bool F64 = false, int DEPTH = 1, class KP>
+// Two fragment buffers: the read of batch n + 1 is issued before the MFMAs of batch n.  A rolling window of two or three batches in flight
+// did not help (-1 % / -7 %: conv3 is not waiting for a single LDS round trip, more reads in flight only lengthen the LDS queue the
+// pipeline's two roles share -- profiles/r05/e_policy_prefetch_depth_ab_not_kept.txt).
+template <int CBIN, int MT, int BATCH, bool SWP = true, bool F64 = false, class KP>
 __device__ __forceinline__ void dconv(const KP &K, const ConvW<CBIN, MT> &W, __bf16 *img, int sample_stride, int in_off, int out_off,
                                       int out_blocks, int flat_c, int ns, int nt_first, int nt_step, int lane, int mt_base, int dummy,
                                       const int *pre = nullptr) {
@@ -160,10 +151,6 @@ __device__ __forceinline__ void dconv(const KP &K, const ConvW<CBIN, MT> &W, __b
             v = zero8();
             if (h == HB) { v[0] = (__bf16)1.0f; v[1] = (__bf16)1.0f; }
         } else {
-            if (PPG_DIRECT_ABLATE & 32) {   // (timing-only build: no fragment reads)
-                v = zero8();
-                v[0] = (__bf16)(float)(c.in_base + ks);
-            } else
             v = *(const bf16x8 *)(img + c.in_base + W.offset(K, ks, pair));
             if (ks == KSB && h == HB) { v = zero8(); v[0] = (__bf16)1.0f; v[1] = (__bf16)1.0f; }
         }
@@ -176,9 +163,6 @@ __device__ __forceinline__ void dconv(const KP &K, const ConvW<CBIN, MT> &W, __b
             for (int j = 0; j < 2; ++j) {   // this lane's channels 32 (mt_base + mt) + 16 h + 8 j .. + 7 = channel block cb0 + 4 mt + j
                 const bool real = c.valid && (cb0 + 4 * mt + j < out_blocks);
                 const int at = !real ? dummy : F64 ? c.out_base + (((cb0 + 4 * mt + j) ^ c.swz) << 3) : c.out_base + (4 * mt + j) * cb_step;
-                if (PPG_DIRECT_ABLATE & 64) {   // (timing-only build: no ReLU / pack / store -- one value kept so that the MFMAs stay)
-                    if (acc[mt][8 * j] == 123.0f) *(float *)(img + dummy) = acc[mt][8 * j];
-                } else
                 *(bf16x8 *)(img + at) = relu_pack8(acc[mt], 8 * j);
             }
     };
@@ -188,18 +172,15 @@ __device__ __forceinline__ void dconv(const KP &K, const ConvW<CBIN, MT> &W, __b
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[mt][r] = 0.0f;
-        constexpr int NSLOT = DEPTH + 1;
-        bf16x8 b[NSLOT][BS];
+        bf16x8 b[2][BS];
 #pragma unroll
-        for (int d = 0; d < DEPTH; ++d)
-#pragma unroll
-            for (int i = 0; i < BS; ++i) if (d * BS + i < KS) b[d][i] = fragment(c, d * BS + i);
+        for (int i = 0; i < BS; ++i) if (i < KS) b[0][i] = fragment(c, i);
         __builtin_amdgcn_sched_barrier(0);   // (keep the reads together and in front: left alone, the scheduler re-pairs each with its MFMA)
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
-            if (nb + DEPTH < NB) {
+            if (nb + 1 < NB) {
 #pragma unroll
-                for (int i = 0; i < BS; ++i) if ((nb + DEPTH) * BS + i < KS) b[(nb + DEPTH) % NSLOT][i] = fragment(c, (nb + DEPTH) * BS + i);
+                for (int i = 0; i < BS; ++i) if ((nb + 1) * BS + i < KS) b[(nb + 1) & 1][i] = fragment(c, (nb + 1) * BS + i);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (nb == 0) between();   // (no fence between the previous tile's epilogue and this batch's MFMAs: the scheduler interleaves them.
@@ -210,7 +191,7 @@ __device__ __forceinline__ void dconv(const KP &K, const ConvW<CBIN, MT> &W, __b
                 if (nb * BS + i < KS) {
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt)
-                        acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W.a[mt][nb * BS + i], b[nb % NSLOT][i], acc[mt], 0, 0, 0);
+                        acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W.a[mt][nb * BS + i], b[nb & 1][i], acc[mt], 0, 0, 0);
                 }
         }
     };
@@ -244,12 +225,11 @@ __device__ __forceinline__ void dconv(const KP &K, const ConvW<CBIN, MT> &W, __b
 // DEEP = true: more than three convolutions: every layer's weights come from L2 when the layer starts.
 template <int OBS, int NCH, bool DEEP>
 __device__ __forceinline__ void direct_main(KPtr Kp, unsigned char *lds) {
-    constexpr bool W1 = PPG_DIRECT_W1, WRES = W1 && !DEEP;   // (DEEP: 512 registers too, but every layer's weights come per sub-group)
+    constexpr bool WRES = !DEEP;         // (DEEP: 512 registers too, but every layer's weights come per sub-group)
     constexpr int MT3 = WRES ? 2 : 1;    // conv3 row tiles per wavefront
-    constexpr int NPOS = W1 ? 2 : 1;     // positions a thread stages per sub-group (ST * P <= 256 NPOS)
+    constexpr int NPOS = 2;              // positions a thread stages per sub-group (ST * P <= 256 NPOS)
     constexpr int HF = WRES ? 18 : 1;    // head fragments of this wavefront that stay in registers
     constexpr int CB1 = NCH > 8 ? 2 : 1;
-    constexpr int B12 = PPG_DIRECT_B12;   // fragments per batch in conv1 / conv2 (0 = all of a tile's at once)
     const auto &K = *Kp;
     const int tid = (int)threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: tile loops, k-step ranges and their branches stay scalar)
@@ -380,42 +360,36 @@ __device__ __forceinline__ void direct_main(KPtr Kp, unsigned char *lds) {
                 }
             }
         };
-        if (!(PPG_DIRECT_ABLATE & 16)) {
-            request(0);
-            stage(0);
-            if (K.ST < nt_samples) request(K.ST);
-        }
+        request(0);
+        stage(0);
+        if (K.ST < nt_samples) request(K.ST);
         __syncthreads();
         PPG_DP(0);
         for (int s0 = 0; s0 < nt_samples; s0 += K.ST) {
             const int ns = (nt_samples - s0) < K.ST ? (nt_samples - s0) : K.ST;
             // ---- convolutions -------------------------------------------------------------------------------------------
-            if (!(PPG_DIRECT_ABLATE & 8)) {
-                if (DEEP) { w1c.load(K, K.wc1, lane); w1c.landed(); }
-                dconv<CB1, 1, B12>(K, w1c, img, sample_stride, K.off_x, n_conv == 1 ? K.off_f : K.off_y, K.cout_blocks[0],
-                                 n_conv == 1 ? K.flat_c : 0, ns, wave, 4, lane, 0, dummy);
-                PPG_DP(1);
-                __syncthreads();
-                PPG_DP(2);
-            }
-            if (n_conv > 1 && !(PPG_DIRECT_ABLATE & 8)) {
+            if (DEEP) { w1c.load(K, K.wc1, lane); w1c.landed(); }
+            dconv<CB1, 1, DIRECT_B12>(K, w1c, img, sample_stride, K.off_x, n_conv == 1 ? K.off_f : K.off_y, K.cout_blocks[0],
+                                      n_conv == 1 ? K.flat_c : 0, ns, wave, 4, lane, 0, dummy);
+            PPG_DP(1);
+            __syncthreads();
+            PPG_DP(2);
+            if (n_conv > 1) {
                 if (DEEP) { w2c.load(K, K.wc2, lane); w2c.landed(); }
-                dconv<2, 1, B12>(K, w2c, img, sample_stride, K.off_y, n_conv == 2 ? K.off_f : K.off_x, K.cout_blocks[1],
-                               n_conv == 2 ? K.flat_c : 0, ns, wave, 4, lane, 0, dummy);
+                dconv<2, 1, DIRECT_B12>(K, w2c, img, sample_stride, K.off_y, n_conv == 2 ? K.off_f : K.off_x, K.cout_blocks[1],
+                                        n_conv == 2 ? K.flat_c : 0, ns, wave, 4, lane, 0, dummy);
                 PPG_DP(3);
                 __syncthreads();
                 PPG_DP(4);
             }
-            if (n_conv > 2 && !(PPG_DIRECT_ABLATE & 4)) {
+            if (n_conv > 2) {
                 if (DEEP) { w3c.load(K, K.wc3, lane, wave >> 1); w3c.landed(); }
                 if (n_conv == 3 && K.flat_c == 64)
-                    dconv<4, MT3, DEEP ? 3 : PPG_DIRECT_B3, true, true>(K, w3c, img, sample_stride, K.off_x, K.off_f, K.cout_blocks[2], 64, ns,
+                    dconv<4, MT3, DEEP ? 3 : DIRECT_B3, true, true>(K, w3c, img, sample_stride, K.off_x, K.off_f, K.cout_blocks[2], 64, ns,
                                                                     WRES ? wave : wave & 1, WRES ? 4 : 2, lane, WRES ? 0 : wave >> 1, dummy);
                 else
-                dconv<4, MT3, DEEP ? 3 : PPG_DIRECT_B3>(K, w3c, img, sample_stride, K.off_x, n_conv == 3 ? K.off_f : K.off_d0, K.cout_blocks[2],
-                                            n_conv == 3 ? K.flat_c : 0, ns, WRES ? wave : wave & 1, WRES ? 4 : 2, lane, WRES ? 0 : wave >> 1, dummy);
-            }
-            if (n_conv > 2 && !(PPG_DIRECT_ABLATE & 4)) {
+                dconv<4, MT3, DEEP ? 3 : DIRECT_B3>(K, w3c, img, sample_stride, K.off_x, n_conv == 3 ? K.off_f : K.off_d0, K.cout_blocks[2],
+                                                    n_conv == 3 ? K.flat_c : 0, ns, WRES ? wave : wave & 1, WRES ? 4 : 2, lane, WRES ? 0 : wave >> 1, dummy);
                 PPG_DP(5);
                 __syncthreads();
                 PPG_DP(6);
@@ -436,7 +410,7 @@ __device__ __forceinline__ void direct_main(KPtr Kp, unsigned char *lds) {
                 }
             }
             // ---- head: partial logits of this wavefront's share of the k-steps; the next sub-group's input goes into X meanwhile ----
-            if (s0 + K.ST < nt_samples && !(PPG_DIRECT_ABLATE & 16)) {
+            if (s0 + K.ST < nt_samples) {
                 stage(s0 + K.ST);
                 PPG_DP(10);
                 if (s0 + 2 * K.ST < nt_samples) request(s0 + 2 * K.ST);
@@ -449,18 +423,15 @@ __device__ __forceinline__ void direct_main(KPtr Kp, unsigned char *lds) {
                 for (int m = 0; m < 2; ++m)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) hacc[m][i] = 0.0f;
-                if (WRES && !(PPG_DIRECT_ABLATE & 1)) {
-                    if (resident) {
-                        bf16x8 fv[HF];
+                if (resident) {
+                    bf16x8 fv[HF];
 #pragma unroll
-                        for (int i = 0; i < HF; ++i) fv[i] = *(const bf16x8 *)(fb + f_koff(K, k_lo + i, kq));
+                    for (int i = 0; i < HF; ++i) fv[i] = *(const bf16x8 *)(fb + f_koff(K, k_lo + i, kq));
 #pragma unroll
-                        for (int i = 0; i < HF; ++i) hacc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hf[i], fv[i], hacc[0], 0, 0, 0);
-                        // (four independent accumulator chains instead of this one: slower, 1751 vs 1225 cycles -- profiles/r04)
-                    }
+                    for (int i = 0; i < HF; ++i) hacc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hf[i], fv[i], hacc[0], 0, 0, 0);
+                    // (four independent accumulator chains instead of this one: slower, 1751 vs 1225 cycles -- profiles/r04)
                 }
-                if (PPG_DIRECT_ABLATE & 1) {
-                } else if (K.head_mt == 1) {
+                if (K.head_mt == 1) {
                     // (k-steps beyond the resident fragments, or all of them: from L2, six requested at once, then their six MFMAs)
                     for (int k0 = k_reg; k0 < k_hi; k0 += 6) {
                         bf16x8 a[6];
@@ -502,7 +473,7 @@ __device__ __forceinline__ void direct_main(KPtr Kp, unsigned char *lds) {
             PPG_DP(8);
             // ---- logits of the sub-group: thread (sample tid >> 4, action tid & 15): bias + the four wavefronts' partial sums in
             // wavefront order -> this workgroup's scratch rows (the actions are chosen for the whole tile at once, below) ----
-            if (smp < ns && !(PPG_DIRECT_ABLATE & 2)) {
+            if (smp < ns) {
                 const int s_local = s0 + smp;
                 for (int m = 0; m < K.head_mt; ++m) {
                     float v = bias_r[m];
@@ -513,50 +484,46 @@ __device__ __forceinline__ void direct_main(KPtr Kp, unsigned char *lds) {
                 }
             }
             PPG_DP(9);
-#ifdef PPG_DIRECT_PROFILE
-            dp_acc[15] += 1;
-#endif
+            PPG_DP_COUNT(15);
             // (no barrier here: the next conv1 reads X and writes Y; `red` is written again three barriers from now)
         }
         // ---- actions of the tile: one lane per sample (argmax, or Gumbel-max with Philox keyed by (seed, env, row)) ----
-        if (!(PPG_DIRECT_ABLATE & 2)) {
-            __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this workgroup's scratch rows have been written ...
-            __syncthreads();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // ... and stale L1 lines of the previous tile's rows are dropped
-            if (tid < nt_samples) {
-                const float *row = lgs + tid * apad;
-                int8_t *dst = (int8_t *)(uintptr_t)tab[2 * tid + 1];
-                uint32_t c_env = 0, c_slot = 0;   // Philox counter of this agent = (global env index, row slot), as in phase_head
-                if (K.sample) {
-                    int k = 0;
+        __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this workgroup's scratch rows have been written ...
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // ... and stale L1 lines of the previous tile's rows are dropped
+        if (tid < nt_samples) {
+            const float *row = lgs + tid * apad;
+            int8_t *dst = (int8_t *)(uintptr_t)tab[2 * tid + 1];
+            uint32_t c_env = 0, c_slot = 0;   // Philox counter of this agent = (global env index, row slot), as in phase_head
+            if (K.sample) {
+                int k = 0;
 #pragma unroll
-                    for (int q = 1; q < MAX_HANDLES; ++q)
-                        if (q < K.n_handles && (uintptr_t)dst >= (uintptr_t)K.actions[q] &&
-                            (uintptr_t)dst < (uintptr_t)K.actions[q] + (size_t)(K.env_base[q + 1] - K.env_base[q]) * (size_t)K.S) k = q;
-                    const uint32_t off = (uint32_t)((uintptr_t)dst - (uintptr_t)K.actions[k]);
-                    const uint32_t b = off / (uint32_t)K.S;
-                    c_env = (uint32_t)K.env_base[k] + b;
-                    c_slot = off - b * (uint32_t)K.S;
-                }
-                uint32_t rnd[4] = {0, 0, 0, 0};
-                int best = 0;
-                float bestv = -INFINITY;
-                for (int a4 = 0; a4 < K.n_actions; a4 += 4) {
-                    const f32x4_t q = *(const GLOBAL_AS f32x4_t *)(row + a4);
-                    if (K.sample) philox(c_env, c_slot, (uint32_t)(a4 >> 2), 0x504F4C31u, K.seed_lo, K.seed_hi, rnd);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        if (a4 + i >= K.n_actions) continue;
-                        float v = q[i];
-                        if (K.sample) {   // Gumbel-max: argmax(logit - log(-log u)) ~ softmax(logits)
-                            const float u = (float)(rnd[i] >> 9) * (1.0f / 8388608.0f) + (1.0f / 16777216.0f);   // 23 bits: 2^-24 <= u < 1, exactly
-                            v -= __logf(-__logf(u));
-                        }
-                        if (v > bestv) { bestv = v; best = a4 + i; }
-                    }
-                }
-                *dst = (int8_t)best;
+                for (int q = 1; q < MAX_HANDLES; ++q)
+                    if (q < K.n_handles && (uintptr_t)dst >= (uintptr_t)K.actions[q] &&
+                        (uintptr_t)dst < (uintptr_t)K.actions[q] + (size_t)(K.env_base[q + 1] - K.env_base[q]) * (size_t)K.S) k = q;
+                const uint32_t off = (uint32_t)((uintptr_t)dst - (uintptr_t)K.actions[k]);
+                const uint32_t b = off / (uint32_t)K.S;
+                c_env = (uint32_t)K.env_base[k] + b;
+                c_slot = off - b * (uint32_t)K.S;
             }
+            uint32_t rnd[4] = {0, 0, 0, 0};
+            int best = 0;
+            float bestv = -INFINITY;
+            for (int a4 = 0; a4 < K.n_actions; a4 += 4) {
+                const f32x4_t q = *(const GLOBAL_AS f32x4_t *)(row + a4);
+                if (K.sample) philox(c_env, c_slot, (uint32_t)(a4 >> 2), 0x504F4C31u, K.seed_lo, K.seed_hi, rnd);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if (a4 + i >= K.n_actions) continue;
+                    float v = q[i];
+                    if (K.sample) {   // Gumbel-max: argmax(logit - log(-log u)) ~ softmax(logits)
+                        const float u = (float)(rnd[i] >> 9) * (1.0f / 8388608.0f) + (1.0f / 16777216.0f);   // 23 bits: 2^-24 <= u < 1, exactly
+                        v -= __logf(-__logf(u));
+                    }
+                    if (v > bestv) { bestv = v; best = a4 + i; }
+                }
+            }
+            *dst = (int8_t)best;
         }
         PPG_DP(0);
     }
@@ -567,7 +534,7 @@ __device__ __forceinline__ void direct_main(KPtr Kp, unsigned char *lds) {
 }
 
 #define PPG_POLICY_DIRECT_KERNEL(name, OBS, NCH, DEEP)                                           \
-    extern "C" __global__ void __launch_bounds__(256, PPG_DIRECT_W1 ? 1 : 2) name(const PolParams K) { \
+    extern "C" __global__ void __launch_bounds__(256, 1) name(const PolParams K) { \
         extern __shared__ __attribute__((aligned(16))) unsigned char lds[];                      \
         direct_main<OBS, NCH, DEEP>((KPtr)__builtin_amdgcn_kernarg_segment_ptr(), lds);          \
     }

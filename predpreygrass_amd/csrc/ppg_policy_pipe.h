@@ -19,58 +19,21 @@
 // drains once per launch.  Same arithmetic in the same order as ppg_policy_direct.h: the logits are bit-identical.
 #pragma once
 
+namespace ppgpol {
+
+// Tuned values of the pipeline (each measured on one GPU at the 4096-env policy step; the alternatives tried and not kept are listed in
+// profiles/EXPERIMENTS.md, "Retired policy-kernel switches").
 // Fragment reads per batch in role A's conv3.  LDS serves requests in arrival order, whatever the priority of the wavefront: five
 // 1 KB reads per role-A wavefront queued at once stand in front of every LDS access of role B's chain (its table reads alone took
 // 1000 cycles per sub-group); batches of 5 / 4 / 3 / 2: 0.362 / 0.356 / 0.350 / 0.347 ms per 4096-env step on one GPU; with area F swizzled and the LDS less crowded,
 // batches of 3 / 2 / 1: 0.340 / 0.321 / 0.314 (profiles/r04)
-#ifndef PPG_PIPE_B3
-#define PPG_PIPE_B3 1
-#endif
-
-#ifndef PPG_PIPE_B12
-#define PPG_PIPE_B12 2      // fragment reads per batch in role B's conv1 / conv2 (0 = a tile's ten at once): 0 / 5 / 4 / 3 / 2 / 1:
-                            // 0.3118 / 0.3129 / 0.3077 / 0.3027 / 0.3007 / 0.3058 ms per step on one GPU (profiles/r04)
-#endif
-#ifndef PPG_PIPE_D3
-#define PPG_PIPE_D3 1       // batches of fragment reads in flight ahead of the MFMAs in role A's conv3 (dconv's DEPTH)
-#endif
-#ifndef PPG_PIPE_D2
-#define PPG_PIPE_D2 1       // the same in role B's conv2
-#endif
-#ifndef PPG_PIPE_CONV2_PAIR
-#define PPG_PIPE_CONV2_PAIR 0   // role B's conv2: 1 = the wavefront's two position tiles as interleaved MFMA chains; 0 = tile after tile (dconv).
-                                // Measured (profiles/r05/e_*): the pair is 1 % SLOWER end to end -- conv2's own phase stays at 1270 cycles
-                                // and role A's conv3 on the same SIMD grows by what role B's denser MFMA stream takes from it
-#endif
-#ifndef PPG_PIPE_HEAD_CHAINS
-#define PPG_PIPE_HEAD_CHAINS 1  // independent accumulator chains of the head's eighteen MFMAs: 2 measured 1 % slower than 1 (profiles/r05/e_*)
-#endif
-#ifndef PPG_PIPE_FETCH_EARLY
-#define PPG_PIPE_FETCH_EARLY 0   // 1: the chunk loads of sub-group it + 2 go out right behind the staging of sub-group it + 1 (experiment, profiles/r05/r_*)
-#endif
-#ifndef PPG_PIPE_ABLATE
-#define PPG_PIPE_ABLATE 0   // timing-only ablation builds (rounds 4-5, profiles/r05/h_*; never the product -- the results are then meaningless):
-                            // 1 no head, 2 no staging, 4 no conv1, 8 no conv2, 16 no conv3, 32 no logits / actions, 64 no Gumbel noise,
-                            // 128 no row fetch / park
-#endif
-#ifndef PPG_PIPE_HOFF
-#define PPG_PIPE_HOFF 0   // 1: the head's eighteen operand offsets in registers instead of recomputed per sub-group -- measured 2 % SLOWER
-                          // (profiles/r05/e_*: eighteen more live registers in role B cost more than the address arithmetic)
-#endif
-#ifndef PPG_PIPE_CONV1X_LOOP
-#define PPG_PIPE_CONV1X_LOOP 0  // conv1x tile after tile (1) instead of the four tiles as one straight line (0)
-#endif
-#ifndef PPG_PIPE_SWP_B
-#define PPG_PIPE_SWP_B true   // role B's convolution loops software-pipelined (the epilogue of tile t behind the reads of tile t + 1)
-#endif
-#ifndef PPG_PIPE_SLEEP
-#define PPG_PIPE_SLEEP 1    // s_sleep argument between two polls of role B's private barrier
-#endif
-#ifndef PPG_PIPE_PRIO_B
-#define PPG_PIPE_PRIO_B 3   // s_setprio of role B's wavefronts (role A: 0)
-#endif
-
-namespace ppgpol {
+constexpr int PIPE_B3 = 1;
+// fragment reads per batch in role B's conv2 (0 = a tile's ten at once): 0 / 5 / 4 / 3 / 2 / 1:
+// 0.3118 / 0.3129 / 0.3077 / 0.3027 / 0.3007 / 0.3058 ms per step on one GPU (profiles/r04)
+constexpr int PIPE_B12 = 2;
+// (0 / 2 and priority 1 measured the same once the roles were balanced: profiles/r05/e_policy_barrier_sleep_priority_batch_ab.txt)
+constexpr int PIPE_SLEEP = 1;    // s_sleep argument between two polls of role B's private barrier
+constexpr int PIPE_PRIO_B = 3;   // s_setprio of role B's wavefronts (role A: 0)
 
 // Role B's private barrier, in two halves: a wavefront ARRIVES (its LDS writes have landed, the counter goes up) and WAITS for the
 // `target`-th arrival later -- with work that does not depend on the other wavefronts in between, the wait finds the counter there.
@@ -93,7 +56,7 @@ __device__ __forceinline__ void pipe_wait(uint32_t *ctr, uint32_t target) {
     int polls = 0;
 #endif
     while ((uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < target) {
-        __builtin_amdgcn_s_sleep(PPG_PIPE_SLEEP);
+        __builtin_amdgcn_s_sleep(PIPE_SLEEP);
 #ifdef PPG_PIPE_DEBUG
         if (++polls > PPG_PIPE_DEBUG_POLLS) {
             if ((threadIdx.x & 63u) == 0 && g_pipe_status && atomicAdd(&g_pipe_status[0], 1u) == 0u) {
@@ -182,8 +145,7 @@ __device__ __forceinline__ u32x2_t relu_pack4(const f32x4_t &a) {
     return w;
 }
 // One sub-group's conv1: X (input blocks at element offset xo) -> Y.  CB1 = 2: a second input block (the ninth channel's taps).
-// LOOP: tile after tile (12 registers of operands) instead of the straight line below.
-template <int CB1, bool LOOP = (PPG_PIPE_CONV1X_LOOP != 0), class KP>
+template <int CB1, class KP>
 __device__ __forceinline__ void conv1x(const KP &K, const Conv1X &W, __bf16 *img, int xo, int ns, int bw, int lane, int dummy) {
     const int kq = lane >> 4;
     const int blk = K.Wp2 * 8;
@@ -191,23 +153,6 @@ __device__ __forceinline__ void conv1x(const KP &K, const Conv1X &W, __bf16 *img
     // the position's own cell of block 1 (CB1 = 1: any cell of block 0 -- its weights are zero)
     const int koff = kq < 3 ? (kq - 1) * 8 : (CB1 > 1 ? blk : 0);
     const int yoff = (kq >> 1) * blk + (kq & 1) * 4;    // where this lane's four output channels go inside the position's Y cells
-    if constexpr (LOOP) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        if (ns <= 0) break;
-        const bool valid = W.smp[t] < ns;
-        const __bf16 *base = img + W.cell[t] + xo + koff;
-        bf16x8 b[3];
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) b[ky] = *(const bf16x8 *)(base + (ky - 1) * K.Wp * 8);
-        f32x4_t acc = W.bias;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(W.a[ky], b[ky], acc, 0, 0, 0);
-        const int at = valid ? W.cell[t] + K.off_y + yoff : dummy;
-        *(u32x2_t *)(img + at) = relu_pack4(acc);
-    }
-    return;
-    }
     // The wavefront's four tiles as ONE straight line: twelve fragment reads in front, then the four tiles' MFMA chains interleaved (a
     // tile's three MFMAs depend on each other through the accumulator: tile by tile the chain ran at the matrix pipe's LATENCY, 290
     // cycles per tile for 48 cycles of issue), then the four epilogues.  Tiles behind the sub-group's last position compute position 0
@@ -231,62 +176,6 @@ __device__ __forceinline__ void conv1x(const KP &K, const Conv1X &W, __bf16 *img
         const bool valid = W.smp[t] < ns;
         const int at = valid ? W.cell[t] + K.off_y + yoff : dummy;
         *(u32x2_t *)(img + at) = relu_pack4(acc[t]);
-    }
-}
-
-// Role B's conv2 (16 -> 32 channels, one 32-row MFMA tile) over the wavefront's TWO position tiles at once: a tile's ten MFMAs depend on
-// each other through its accumulators (64 cycles from one to the next), so tile after tile the layer ran at that latency -- 1270 cycles
-// for 640 of issue.  Two independent chains interleaved fill the gaps.  Fragment reads two k-steps (four reads) ahead.
-template <class KP>
-__device__ __forceinline__ void conv2_pair(const KP &K, const ConvW<2, 1> &W, __bf16 *img, int in_off, int out_off, int out_blocks, int ns,
-                                           int bw, int lane, int dummy, const int *cells) {
-    constexpr int KS = ConvW<2, 1>::KS, KSB = ConvW<2, 1>::KS_BIAS, HB = ConvW<2, 1>::H_BIAS;
-    const int h = lane >> 5;
-    const int blk = K.Wp2 * 8;
-    if (ns <= 0) return;
-    const int in0 = in_off + h * blk;
-    const int cb0 = 2 * h;
-    auto fragment = [&](int cell, int ks) -> bf16x8 {
-        bf16x8 v;
-        if (ks == KSB && HB == 0) {   // (the whole k-step is the bias block + nothing)
-            v = zero8();
-            if (h == HB) { v[0] = (__bf16)1.0f; v[1] = (__bf16)1.0f; }
-        } else {
-            v = *(const bf16x8 *)(img + cell + in0 + W.offset(K, ks, 2 * blk));
-            if (ks == KSB && h == HB) { v = zero8(); v[0] = (__bf16)1.0f; v[1] = (__bf16)1.0f; }
-        }
-        return v;
-    };
-    f32x16 acc[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-    bf16x8 b[3][2];   // a rolling window of three k-steps x two tiles
-#pragma unroll
-    for (int d = 0; d < 2; ++d)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) b[d][t] = fragment(cells[2 * t], d);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        if (ks + 2 < KS) {
-#pragma unroll
-            for (int t = 0; t < 2; ++t) b[(ks + 2) % 3][t] = fragment(cells[2 * t], ks + 2);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W.a[0][ks], b[ks % 3][t], acc[t], 0, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const bool valid = cells[4 + t] < ns;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const bool real = valid && (cb0 + j < out_blocks);
-            const int at = real ? cells[2 * t] + out_off + (cb0 + j) * blk : dummy;
-            *(bf16x8 *)(img + at) = relu_pack8(acc[t], 8 * j);
-        }
     }
 }
 
@@ -470,7 +359,7 @@ __device__ __forceinline__ void pipe_main(KPtr Kp, unsigned char *lds, int wg = 
                 // actions.  The Gumbel noise was computed one iteration ago by ANOTHER wavefront (below) and waits in LDS.
                 // Its LDS reads (partial sums, table entry, noise: complete since the iteration's barrier) are issued HERE, in front of
                 // conv3, and consumed behind it: three dependent LDS round trips less on the wavefronts that carry the most work.
-                const bool do_act = !(PPG_PIPE_ABLATE & 32) && it >= 2 && 4 * wave < K.ST && 4 * wave < nt_samples - (it - 2) * K.ST;   // (this wavefront's four samples: 4 wave .. 4 wave + 3)
+                const bool do_act = it >= 2 && 4 * wave < K.ST && 4 * wave < nt_samples - (it - 2) * K.ST;   // (this wavefront's four samples: 4 wave .. 4 wave + 3)
                 float act_part[4] = {0.0f, 0.0f, 0.0f, 0.0f}, act_noise = 0.0f;
                 unsigned long long act_er = 0;
                 int act_ns = 0, act_s_local = 0;
@@ -485,14 +374,14 @@ __device__ __forceinline__ void pipe_main(KPtr Kp, unsigned char *lds, int wg = 
                     if (K.sample) act_noise = noise[(g & 1) * 256 + btid];
                 }
                 PPG_DP(3);
-                if (!(PPG_PIPE_ABLATE & 16) && it >= 0 && it < G) {
+                if (it >= 0 && it < G) {
                     const int left = nt_samples - it * K.ST, ns = left < K.ST ? left : K.ST;
                     if (K.flat_c == 64)
-                        dconv<4, 2, PPG_PIPE_B3, false, true, PPG_PIPE_D3>(K, w3c, img, sample_stride, (it & 1) ? K.pipe_x1 : 0, (it & 1) ? K.pipe_f1 : K.off_f,
-                                                              K.cout_blocks[2], 64, ns, wave, 4, lane, 0, dummy, cells);
+                        dconv<4, 2, PIPE_B3, false, true>(K, w3c, img, sample_stride, (it & 1) ? K.pipe_x1 : 0, (it & 1) ? K.pipe_f1 : K.off_f,
+                                                          K.cout_blocks[2], 64, ns, wave, 4, lane, 0, dummy, cells);
                     else
-                    dconv<4, 2, PPG_PIPE_B3, false, false, PPG_PIPE_D3>(K, w3c, img, sample_stride, (it & 1) ? K.pipe_x1 : 0, (it & 1) ? K.pipe_f1 : K.off_f,
-                                                      K.cout_blocks[2], K.flat_c, ns, wave, 4, lane, 0, dummy);
+                    dconv<4, 2, PIPE_B3, false, false>(K, w3c, img, sample_stride, (it & 1) ? K.pipe_x1 : 0, (it & 1) ? K.pipe_f1 : K.off_f,
+                                                       K.cout_blocks[2], K.flat_c, ns, wave, 4, lane, 0, dummy);
                 }
                 PPG_DP(1);
                 if (do_act) {
@@ -531,7 +420,7 @@ __device__ __forceinline__ void pipe_main(KPtr Kp, unsigned char *lds, int wg = 
                 // Gumbel noise of sub-group it - 1 (needed in the next iteration): -log(-log u), u from Philox keyed by (seed, env, row
                 // slot, action) as in phase_head.  Sample s is served by wavefront (s / 4 + 2) & 3: with 7 samples per sub-group the
                 // wavefronts 2, 3 -- which have no sample to pick actions for and would wait at the barrier -- do all of it.
-                if (!(PPG_PIPE_ABLATE & 64) && K.sample && it >= 1 && it - 1 < G) {
+                if (K.sample && it >= 1 && it - 1 < G) {
                     const int g = it - 1, left = nt_samples - g * K.ST, ns = left < K.ST ? left : K.ST;
                     const int s0 = 4 * ((wave + 2) & 3);
                     if (s0 < ns) {
@@ -555,7 +444,7 @@ __device__ __forceinline__ void pipe_main(KPtr Kp, unsigned char *lds, int wg = 
     // ================= role B: rows -> X, conv1, conv2; head =================
     // Role B is the longer chain, and its MFMAs are few and dependent: with equal priorities the SIMD serves role A's dense MFMA stream
     // first and the head's 18 MFMAs take as long as the whole of conv3 (profiles/r04) -- B goes first whenever it has something to issue.
-    __builtin_amdgcn_s_setprio(PPG_PIPE_PRIO_B);
+    __builtin_amdgcn_s_setprio(PIPE_PRIO_B);
     Conv1X w1x;
     ConvW<2, 1> w2c;
     bf16x8 hf[HF];
@@ -573,11 +462,6 @@ __device__ __forceinline__ void pipe_main(KPtr Kp, unsigned char *lds, int wg = 
         hf[i] = __builtin_bit_cast(bf16x8, v);
     }
     uint32_t b_target = 0;
-#if PPG_PIPE_HOFF
-    int hoff[HF];   // where this lane's eighteen head operands lie in a sample's area F: the same in every sub-group -- once per launch
-#pragma unroll
-    for (int i = 0; i < HF; ++i) { hoff[i] = f_koff(K, k_lo + i, kq); __asm__ volatile("" : "+v"(hoff[i])); }
-#endif
     int cells[6];   // (as in role A: the positions of this wavefront's two tiles, once per launch)
     dconv_cells(K, sample_stride, bw, 4, lane, cells);
     // bfloat16 rows whose size is a multiple of 8 bytes (K.pipe_ni > 0) come in as they lie in HBM: ALIGNED 8-byte chunks, consecutive
@@ -685,41 +569,25 @@ __device__ __forceinline__ void pipe_main(KPtr Kp, unsigned char *lds, int wg = 
             // fetch -> WAIT -> conv2: the waits of the two private barriers find most arrivals done
             const bool more = it + 1 < G;   // sub-group it + 1: rows -> X, conv1, conv2
             if (more) {
-                if (!(PPG_PIPE_ABLATE & 2)) stage(it + 1);
+                stage(it + 1);
                 b_target += 4;
                 pipe_arrive(ctr, lane);
-#if PPG_PIPE_FETCH_EARLY
-                if constexpr (CH) fetch(it + 2 < G ? it + 2 : G - 1);
-#endif
             }
             PPG_DP(11);
-            if (!(PPG_PIPE_ABLATE & 1) && it >= 1 && it - 1 < G) {   // head of sub-group it - 1: this wavefront's k-steps
+            if (it >= 1 && it - 1 < G) {   // head of sub-group it - 1: this wavefront's k-steps
                 const int g = it - 1, ns = group_ns(g);
                 const __bf16 *fb = img + __mul24(colh < ns ? colh : 0, sample_stride) + ((g & 1) ? K.pipe_f1 : K.off_f);
-                f32x4_t hacc, hacc1;
+                f32x4_t hacc;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) { hacc[i] = 0.0f; hacc1[i] = 0.0f; }
+                for (int i = 0; i < 4; ++i) hacc[i] = 0.0f;
+                // (the operand offsets are recomputed per sub-group: eighteen registers that hold them measured 2 % slower; ONE accumulator
+                //  chain, as in the one-role kernels: two measured 1 % slower and are not bit-identical -- profiles/r05/
+                //  e_policy_head_offsets_in_registers_ab_not_kept.txt, e_policy_chain_interleaving_ab_not_kept.txt)
                 bf16x8 fv[HF];
 #pragma unroll
-#if PPG_PIPE_HOFF
-                for (int i = 0; i < HF; ++i) fv[i] = *(const bf16x8 *)(fb + hoff[i]);
-#else
                 for (int i = 0; i < HF; ++i) fv[i] = *(const bf16x8 *)(fb + f_koff(K, k_lo + i, kq));
-#endif
-                if (PPG_PIPE_HEAD_CHAINS == 2) {
-                    // two chains (k-steps 0-8, 9-17), added at the end: the SAME partial sums as one chain of eighteen would NOT come out bit
-                    // for bit -- the one-role kernels keep one chain; the logits differ in the last bits (tests: tolerance, not equality)
-#pragma unroll
-                    for (int i = 0; i < HF / 2; ++i) {
-                        hacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hf[i], fv[i], hacc, 0, 0, 0);
-                        hacc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hf[HF / 2 + i], fv[HF / 2 + i], hacc1, 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) hacc[i] += hacc1[i];
-                } else {
 #pragma unroll
                 for (int i = 0; i < HF; ++i) hacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hf[i], fv[i], hacc, 0, 0, 0);
-                }
                 float *wr = red + (g & 1) * 1024;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) wr[(bw * 16 + 4 * kq + i) * 16 + colh] = hacc[i];
@@ -729,35 +597,27 @@ __device__ __forceinline__ void pipe_main(KPtr Kp, unsigned char *lds, int wg = 
                 const int g = it + 1, ns = group_ns(g), xo = (g & 1) ? K.pipe_x1 : 0;
                 pipe_wait(ctr, b_target);
                 PPG_DP(6);
-                if (!(PPG_PIPE_ABLATE & 4)) conv1x<CB1>(K, w1x, img, xo, ns, bw, lane, dummy);
+                conv1x<CB1>(K, w1x, img, xo, ns, bw, lane, dummy);
                 PPG_DP(7);
                 b_target += 4;
                 pipe_arrive(ctr, lane);
-                if (PPG_PIPE_ABLATE & 128) { }
-#if PPG_PIPE_FETCH_EARLY
-                else if constexpr (CH) { }
-#else
-                else if constexpr (CH) fetch(g + 1 < G ? g + 1 : g);   // (unconditional, like the loads in it; the last one is not parked)
-#endif
+                // (the row fetch here; right behind the staging, a whole iteration ahead, was not faster:
+                //  profiles/r05/e_policy_fetch_a_whole_iteration_ahead_ab_not_kept.txt)
+                if constexpr (CH) fetch(g + 1 < G ? g + 1 : g);   // (unconditional, like the loads in it; the last one is not parked)
                 else if (g + 1 < G) request(g + 1);
                 PPG_DP(5);
                 pipe_wait(ctr, b_target);
                 PPG_DP(8);
-#if PPG_PIPE_CONV2_PAIR
-                conv2_pair(K, w2c, img, K.off_y, xo, K.cout_blocks[1], ns, bw, lane, dummy, cells);
-#else
-                if (!(PPG_PIPE_ABLATE & 8))
-                dconv<2, 1, PPG_PIPE_B12, PPG_PIPE_SWP_B, false, PPG_PIPE_D2>(K, w2c, img, sample_stride, K.off_y, xo, K.cout_blocks[1], 0, ns, bw, 4, lane, 0, dummy, cells);
-#endif
+                // software-pipelined, tile after tile (the wavefront's two tiles as interleaved MFMA chains measured 1 % slower end to end:
+                // conv2's own phase stayed at 1270 cycles and role A's conv3 on the same SIMD grew --
+                // profiles/r05/e_policy_chain_interleaving_ab_not_kept.txt)
+                dconv<2, 1, PIPE_B12, true, false>(K, w2c, img, sample_stride, K.off_y, xo, K.cout_blocks[1], 0, ns, bw, 4, lane, 0, dummy, cells);
                 PPG_DP(9);
-                if (PPG_PIPE_ABLATE & 128) { }
-                else if constexpr (CH) park(g + 1, g + 1 < G);   // (every B wavefront has staged sub-group g out of `raw`: two private barriers ago)
+                if constexpr (CH) park(g + 1, g + 1 < G);   // (every B wavefront has staged sub-group g out of `raw`: two private barriers ago)
             }
             __syncthreads();
             PPG_DP(10);
-#ifdef PPG_DIRECT_PROFILE
-            dp_acc[15] += 1;
-#endif
+            PPG_DP_COUNT(15);
         }
     }
     };
