@@ -1,6 +1,3 @@
-#ifndef PPG_COOP_QUAD32
-#define PPG_COOP_QUAD32 1
-#endif
 // ppg_env_coop.h -- part of struct ppg::Env (ppg_kernel.h includes it INSIDE the struct's body: member functions, no include guard,
 // not a header of its own): the cooperative kernels' observation writing: whole 1 KB pieces of an env's run of live rows, both env-region layouts.
     // ---- COOP: observations as whole 1 KB pieces of an env's run of live rows ---------------------------------
@@ -12,18 +9,15 @@
     // (BASE:520-523), from the agent's position and the element's window offsets alone.  This wavefront writes pieces first,
     // first + stride, ...
     // elements per piece: 128 (two per lane); 256 for the second generation's float32 rows on the four-map layout (four per lane)
-    static constexpr bool QUAD32 = PPG_COOP_QUAD32 && GEN2 && CH0MAP && COOP && !WALLS;
+    static constexpr bool QUAD32 = GEN2 && CH0MAP && COOP && !WALLS;
     PPG_MEMBER int piece_shift() const { return (QUAD32 && P.obs_f32 == 1) ? 8 : 7; }
     // Who writes which piece: statically -- this wavefront writes pieces first, first + stride, ... (tk == nullptr: mid-step
     // observations, the fused kernels) -- or through an LDS ticket word (DYN): a ticket is U consecutive pieces, and the next ticket is
     // issued before the pieces in hand are produced, so its round trip hides behind them.
-#ifndef PPG_COOP_TICKET_GROUPS
-#define PPG_COOP_TICKET_GROUPS 4
-#endif
     // a ticket of the piece writer is TG groups of U consecutive pieces (one LDS round trip per 1-2 K elements: second generation
     // +1.5-2 %, 64x64 grids +1.2 % against one group per ticket, headline equal; the walls variant's chunks of 256 window cells are
     // large enough as they are -- there larger tickets cost 2 % of balance: profiles/r06/y_*)
-    static constexpr int TG = PPG_COOP_TICKET_GROUPS;
+    static constexpr int TG = 4;
     struct Turn {
         uint32_t *tk; int stride, us, end, take; uint32_t pend;
     };
@@ -242,38 +236,16 @@
             }
         }
     }
-    // after the workgroup barrier: all the workgroup's envs, piece p of the workgroup to wavefront p mod NW
-    // WALLS (ppgc3_step): whole rows instead of pieces -- row i of the workgroup to wavefront i mod NW, each through obs_row_walls_in
-    // (its per-cell work -- wall bit, line-of-sight bit, three lookups -- feeds all 4 / 5 channels of the cell)
+    // the fused kernels, after the workgroup barrier: all the workgroup's envs, piece p of the workgroup to wavefront p mod NW
     PPG_MEMBER void coop_write_all(unsigned char *wg_lds) {
-        int at = 0;   // pieces (WALLS: rows) handed out so far, mod NW
+        static_assert(!WALLS, "the cooperative walls kernel is never fused: it writes through coop_write_dynamic");
+        int at = 0;   // pieces handed out so far, mod NW
         for (int k = 0; k < C.coop_e; ++k) {
             const uint32_t *slot = ctl + CTL_SLOT + 4 * k;
             const int eb = (int)wv::first(slot[2]);
             if (eb < 0) continue;
             unsigned char *region = wg_lds + (size_t)k * C.lds_env_bytes;
             const uint32_t *lst = (const uint32_t *)(region + P.off_scr);
-            if (WALLS) {
-                const bool flat = walls_flat();
-                const uint32_t *vm = (const uint32_t *)(region + C.off_vm);
-#pragma unroll
-                for (int type = 0; type < 2; ++type) {
-                    const int n_live = (int)wv::first(slot[type]);
-                    int first = wave_idx - at;
-                    if (first < 0) first += NW;
-                    if (flat) {   // runs of window cells, 64 per pass (obs_cells_walls)
-                        obs_cells_walls(type, lst + (type ? 64 : 0), n_live, vm + (type ? 64 * C.vis_words : 0), region, eb, first, NW);
-                        at = (at + walls_chunks(type, n_live)) % NW;
-                        continue;
-                    }
-                    for (int i = first; i < n_live; i += NW) {   // (no precomputed masks: whole rows, each walks its lines)
-                        const uint32_t en = wv::first(lst[(type ? 64 : 0) + i]);
-                        obs_row_walls_in(type, (int)(en >> 16), en & 0xFFFFu, region, eb);
-                    }
-                    at = (at + n_live) % NW;
-                }
-                continue;
-            }
 #pragma unroll
             for (int type = 0; type < 2; ++type) {
                 const int n_live = (int)wv::first(slot[type]);

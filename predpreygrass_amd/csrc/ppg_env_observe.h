@@ -64,13 +64,6 @@
         for (int c = 0; c < NCH; ++c)
 #pragma unroll
             for (int h = 0; h < 2; ++h) v[c][h] = val[idx[c][h]];
-#ifdef PPG_EXP_NO_OBS_READS  // ablation build only (tools/exp_variants.py): stores without LDS lookups
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) { v[c][0] = 0.0; v[c][1] = 0.0; }
-#endif
-#ifdef PPG_EXP_NO_OBS_STORES  // ablation build only: no observation stores at all
-        if (P.batch > 0) { wv::sync(); return; }
-#endif
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             if (lutr[BASE + 2 * c] & 0x4000000u) {
@@ -108,9 +101,6 @@
     PPG_MEMBER double window_sum(int type, int ch, uint32_t s_xy) {
         // (not `type ? P.Rq : P.Rp`: with a run-time type hipcc selects the fields' ADDRESSES and spills both to scratch)
         const int R = P.Rp + (type ? P.Rq - P.Rp : 0), n = R * R;
-#ifdef PPG_EXP_DRIVE_NO_SUM  // ablation build only: what the window sums cost altogether
-        if (P.batch > 0) return 0.0;
-#endif
         const int x = (int)(s_xy >> 8), y = (int)(s_xy & 255u);
         const int s_cell = x * P.G + y;
         const int rmax = P.Rp > P.Rq ? P.Rp : P.Rq;   // one staging area per wave of a multi-wave workgroup
@@ -127,9 +117,6 @@
         }
         wv::sync();
         double res;
-#ifdef PPG_EXP_DRIVE_NO_REDUCE  // ablation build only: staging without the ordered reduction
-        if (P.batch > 0) { res = first_f64(win[0]); wv::sync(); return res; }
-#endif
         if (n <= 128) {
             res = np_sum_block(win, 0, n);
         } else {
@@ -255,13 +242,10 @@
     // instructions the memory pipeline takes (profiles/r06/v_*).  A row's R*R cells are cut into ceil(R*R / WQ) quads; the last quad
     // of a row starts at R*R - WQ, i.e. overlaps its neighbour and writes up to WQ - 1 cells a second time with the same values, so
     // every quad is whole and there is one store path.
-#ifndef PPG_WALLS_QUAD
-#define PPG_WALLS_QUAD 4
-#endif
-    static constexpr int WQ = PPG_WALLS_QUAD;
+    static constexpr int WQ = 4;
     PPG_MEMBER bool walls_quads(int type) const {
         const int R = P.Rp + (type ? P.Rq - P.Rp : 0);
-        return WQ > 1 && P.obs_f32 == 1 && R * R >= WQ;
+        return P.obs_f32 == 1 && R * R >= WQ;
     }
     // 64-lane chunks of a species' run of n_live rows (what obs_cells_walls hands out to the wavefronts)
     PPG_MEMBER int walls_chunks(int type, int n_live) const {
@@ -271,7 +255,7 @@
     }
     PPG_MEMBER void obs_quads_walls(int type, const uint32_t *list, int n_live, const uint32_t *vm, const unsigned char *region, int eb,
                                     int first, int stride, uint32_t *tk = nullptr) {
-        typedef float fq_t __attribute__((vector_size((WQ > 1 ? WQ : 2) * 4), aligned(4)));   // (4-byte aligned: rows of R*R cells start anywhere)
+        typedef float fq_t __attribute__((vector_size(WQ * 4), aligned(4)));   // (4-byte aligned: rows of R*R cells start anywhere)
         const int R = P.Rp + (type ? P.Rq - P.Rp : 0);
         const uint32_t rmagic = C.rp_magic + (type ? C.rq_magic - C.rp_magic : 0u);
         const int n = R * R, off = (R - 1) / 2, Wc = 2 * off + 1;

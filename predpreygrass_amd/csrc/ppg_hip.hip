@@ -1,32 +1,32 @@
 // ppg_hip.hip -- libppg_hip.so: the gfx950 kernels and the HIP backend of include/ppg.h.
 //
-// Build (see __graft_entry__.build_hip): every unit with
-//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c   (ppg_hip.hip, and ppg_kernels.hip once per
-//   -DPPG_TU_GEN=1|2 -DPPG_TU_NQ=1|2|4), then hipcc -shared -o libppg_hip.so *.o
+// Build (see __graft_entry__.build_hip): this unit and ppg_kernels.hip once per (PPG_TU_GEN, PPG_TU_NQ) pair, each with
+//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c, then hipcc -shared -o libppg_hip.so *.o
 // -ffp-contract=off: energies are IEEE float64 sums that must round exactly like CPython's.
 #include <hip/hip_runtime.h>
 
 #include "ppg_host.h"
 
 // The kernels are compiled in separate translation units (ppg_kernels.hip, one per generation and prey-register
-// count) so that the build runs in parallel; this unit holds the host side and only declares them.
+// count) so that the build runs in parallel; this unit holds the host side and only declares them (the register caps are ppg_kernels.hip's).
 // kernel name: ppg_<mode>_[p2]q<prey registers>[g]   (g = generic observation geometry, descriptors in LDS; p2 = 128 predator rows);
 // ppg2_* = second generation (two agent types, stochastic reproduction)
-#define PPG_K(name, NQ, MODE, FAST) PPG_KERNEL(name, (NQ <= 2 ? 4 : 2))(const ppg::KParams P);
-#define PPG_K2(name, NQ, MODE, FAST) PPG_KERNEL(name, (NQ <= 2 ? 4 : 2))(const ppg::KParams P);
-#define PPG_K3(name, NQ, MODE) PPG_KERNEL(name, (NQ <= 2 ? 4 : 2))(const ppg::KParams P);
-#define PPG_K4(name, NQ, MODE) PPG_KERNEL(name, (NQ <= 2 ? 4 : 2))(const ppg::KParams P);
-#define PPG_KW3(name, NQ, NW) PPG_KERNEL_NW(name, (NQ <= 2 ? 4 : 2), NW)(const ppg::KParams P);
-#define PPG_KW4(name, NQ, NW) PPG_KERNEL_NW(name, (NQ <= 2 ? 4 : 2), NW)(const ppg::KParams P);
-#define PPG_KW(name, NQ, FAST, NW) PPG_KERNEL_NW(name, (NQ <= 2 ? 4 : 2), NW)(const ppg::KParams P);
-#define PPG_KW2(name, NQ, FAST, NW) PPG_KERNEL_NW(name, (NQ <= 2 ? 4 : 2), NW)(const ppg::KParams P);
-#define PPG_KC(name, NQ, GEN2, NW) PPG_KERNEL_NW(name, 4, NW)(const ppg::KParams P);
-#define PPG_KC3(name, NQ) PPG_KERNEL_NW(name, 4, 4)(const ppg::KParams P);
-#define PPG_KCM(name, NQ, GEN2) PPG_KERNEL_NW(name, 4, 4)(const ppg::KParams P);
-#define PPG_KCH(name, NQ) PPG_KERNEL_NW(name, 8, 4)(const ppg::KParams P);
-#define PPG_KCR(name, NQ, GEN2, NW) PPG_KERNEL_NW(name, 4, NW)(const ppg::KParams P);
-#define PPG_KP(name, NQ, MODE) PPG_KERNEL(name, (NQ <= 2 ? 4 : 2))(const ppg::KParams P);
-#define PPG_KP2(name, NQ, MODE) PPG_KERNEL(name, (NQ <= 2 ? 4 : 2))(const ppg::KParams P);
+#define PPG_DECLARE_KERNEL(name) extern "C" __global__ void name(const ppg::KParams P);
+#define PPG_K(name, NQ, MODE, FAST) PPG_DECLARE_KERNEL(name)
+#define PPG_K2(name, NQ, MODE, FAST) PPG_DECLARE_KERNEL(name)
+#define PPG_K3(name, NQ, MODE) PPG_DECLARE_KERNEL(name)
+#define PPG_K4(name, NQ, MODE) PPG_DECLARE_KERNEL(name)
+#define PPG_KW3(name, NQ, NW) PPG_DECLARE_KERNEL(name)
+#define PPG_KW4(name, NQ, NW) PPG_DECLARE_KERNEL(name)
+#define PPG_KW(name, NQ, FAST, NW) PPG_DECLARE_KERNEL(name)
+#define PPG_KW2(name, NQ, FAST, NW) PPG_DECLARE_KERNEL(name)
+#define PPG_KC(name, NQ, GEN2, NW) PPG_DECLARE_KERNEL(name)
+#define PPG_KC3(name, NQ) PPG_DECLARE_KERNEL(name)
+#define PPG_KCM(name, NQ, GEN2) PPG_DECLARE_KERNEL(name)
+#define PPG_KCH(name, NQ) PPG_DECLARE_KERNEL(name)
+#define PPG_KCR(name, NQ, GEN2, NW) PPG_DECLARE_KERNEL(name)
+#define PPG_KP(name, NQ, MODE) PPG_DECLARE_KERNEL(name)
+#define PPG_KP2(name, NQ, MODE) PPG_DECLARE_KERNEL(name)
 #include "ppg_kernel_list.h"
 
 PPG_DEFINE_KERNELSC(1)

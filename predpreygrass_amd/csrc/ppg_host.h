@@ -42,8 +42,6 @@ struct ppg_handle {
     uint32_t *coop_tab_dev;   // library-owned: KParams::coop_tab of both layouts
     int32_t drive;  // drive-conditioned variant of the base family (cfg.n_drive)
     int32_t envs_in_flight;  // scheduling hint (ppg_set_envs_in_flight); 0 = the handle's own batch
-    int32_t coop_wgs_per_cu;  // float64 / float32 rows: four-wave cooperative workgroups a CU takes at most (PPG_COOP_WGS_PER_CU, read at create)
-    int32_t step_lds_pad;     // experiment (PPG_STEP_LDS_PAD, read at create): unused LDS added to the multi-wave kernels' launches
     int32_t *order_dev;      // library-owned [batch]: env order of ppg_rebalance (NULL until first used)
     int32_t *resident_dev;   // library-owned word: KParams::resident_envs (allocated at create; the kernels see it once it has been written)
     int32_t resident_host;   // staging word of ppg_set_resident_envs / ppg_get_resident_envs
@@ -674,10 +672,7 @@ static int ppg_create_common(const ppg_config *cfg, const ppg_config_gen2 *cfg2,
     h->coop_ok = 0; h->coop3_ok = 0; h->coop_prefers3 = 0; h->coop3_tab_off = 0; h->coop_tab_dev = nullptr;
     h->forced = {0, 0, 0};
     h->envs_in_flight = 0;
-    {   // scheduling knobs of the experiments, read ONCE per handle (never per step)
-        const char *ev = getenv("PPG_COOP_WGS_PER_CU"), *pad = getenv("PPG_STEP_LDS_PAD");
-        h->coop_wgs_per_cu = ev ? atoi(ev) : 5;
-        h->step_lds_pad = pad ? atoi(pad) : 0;
+    {   // the environment's knobs, read ONCE per handle (never per step)
         const char *pf = getenv("PPG_BACKWARD_PREFETCH");   // (A/B of ppg_backward's load placement: profiles/EXPERIMENTS.md)
         h->backward_prefetch = pf ? (atoi(pf) != 0) : 1;
         h->backward_samples_prefetch = pf ? (atoi(pf) != 0) : 0;   // (ppg_backward_samples: measured slower one step ahead, same record)
@@ -828,21 +823,18 @@ static ppg::KParams ppg_planned_step_params(const ppg_handle *h, bool fused = fa
         // float64 / float32 rows: at most FIVE four-wave workgroups (ten envs) per CU although registers and LDS admit six -- a CU
         // then has fewer scattered write streams open at a time: 66.8 -> 68.2 M env-steps/s on the headline workload, the driver's
         // command 62.1 -> 63.0 M (profiles/r05/n_coop_workgroups_per_cu.txt; four: the same; three: -13 %).  Done by asking for LDS
-        // the kernel does not use.  bfloat16 rows go the other way (ppgch_step: eight per CU).  PPG_COOP_WGS_PER_CU=0: no limit.
+        // the kernel does not use.  bfloat16 rows go the other way (ppgch_step: eight per CU).
         // (obs_f32: the handle's normalised row dtype, both generations -- 0 float64, 1 float32, 2 / 3 bfloat16)
+        static constexpr int COOP_WGS_PER_CU = 5;
         if (wp.nw == 4 && h->base.obs_f32 < 2) {
-            const int per_cu = h->coop_wgs_per_cu;
-            if (per_cu > 0 && per_cu < 16) {
-                const int floor_bytes = 160 * 1024 / (per_cu + 1) + 16;
-                if (P.lds_bytes < floor_bytes) P.lds_bytes = floor_bytes;
-            }
+            const int floor_bytes = 160 * 1024 / (COOP_WGS_PER_CU + 1) + 16;
+            if (P.lds_bytes < floor_bytes) P.lds_bytes = floor_bytes;
         }
         P.env_order = h->base.env_order;
         P.resident_envs = fused ? nullptr : h->base.resident_envs;   // (the fused kernels keep plain stores)
         P.vis_masks = h->base.vis_masks;
         P.vis_env_stride = h->base.vis_env_stride;
     }
-    else P.lds_bytes += h->step_lds_pad;   // experiment (profiles/r05/s_*): fewer envs per CU for the multi-wave kernels
     P.helper_min_rows = wp.min_rows;
     return P;
 }
@@ -988,7 +980,6 @@ int ppg_walls_changed(ppg_handle *h, void *stream) {
     free(bits);
     if (rc != PPG_OK) return rc;
     h->base.vis_masks = h->vis_dev;   // every later launch reads the masks instead of walking the lines
-    if (getenv("PPG_VIS_PER_ENV")) same = false;   // (A/B switch: every env reads its own table whatever the bitmaps say)
     h->base.vis_env_stride = same ? 0 : B.G * B.G;
     return rc;
 }
@@ -1037,7 +1028,7 @@ int32_t ppg_lds_bytes(const ppg_handle *h) { return h ? h->base.lds_bytes : 0; }
 
 // bfloat16 rows on the four-wave cooperative kernel: its 64-register build when eight workgroups fit a CU's LDS
 static bool ppg_coop_high_occupancy(const ppg_handle *h, int coop_e) {
-    return !h->gen2 && h->cfg.obs_dtype >= 2 && ppg_coop_lds_bytes_of(h->coop, coop_e) * 8 <= 160 * 1024 && !getenv("PPG_COOP_NO_HIGH_OCCUPANCY");
+    return !h->gen2 && h->cfg.obs_dtype >= 2 && ppg_coop_lds_bytes_of(h->coop, coop_e) * 8 <= 160 * 1024;
 }
 
 const char *ppg_step_kernel_name(ppg_handle *h) {

@@ -343,12 +343,9 @@ struct Env {
     // but that is a second dependent memory round trip per call, and under a saturated memory system a round trip is 5-10 k cycles.
     // Round 5: the multi-wave kernels of the base family too (BASELINE configs 2 and 4: ppgw16_step / ppgwp_step) -- their phase profiles
     // (profiles/r05) show the "store" phase, i.e. this read-back, at 16-18 % of a wavefront's transition.
-#ifndef PPG_CARRY_CUM_MULTIWAVE
-#define PPG_CARRY_CUM_MULTIWAVE 1
-#endif
     // (round 6, measured and not kept: the walls variant's four-wave kernel too -- 94.3 against 92.3 us per 4096-env step at its
     // 64-register cap, six more row registers spill; 102 us at 80 registers: profiles/r06/g_*)
-    static constexpr bool CARRY_CUM = COOP || (PPG_CARRY_CUM_MULTIWAVE && NW > 1 && !GEN2 && !WALLS && !DRIVE && !KICK && NQ <= 2);
+    static constexpr bool CARRY_CUM = COOP || (NW > 1 && !GEN2 && !WALLS && !DRIVE && !KICK && NQ <= 2);
     template <bool B8, class Dummy = void> struct MapElem { typedef uint16_t type; };
     template <class Dummy> struct MapElem<true, Dummy> { typedef uint8_t type; };
     typedef typename MapElem<MAP8>::type map_t;
@@ -379,16 +376,7 @@ struct Env {
     // every wavefront of the workgroup takes pieces of the envs that are ready through LDS tickets: while one of the workgroup's
     // transitions is still running, the other env's observations are already being written by the three wavefronts that are free
     // (behind a barrier they waited -- 5-7 % of a wavefront's cycles on average, far more in the slow tail).
-#ifndef PPG_COOP_DYNAMIC
-#define PPG_COOP_DYNAMIC 1
-#endif
-// the table stores of a transition wavefront are issued right after its READY bit, before it joins the writing (they need registers
-// only; with no barrier behind them they delay nobody else and complete under the write phase instead of at the workgroup's tail:
-// second generation +3.3 %, walls +2.8 %, 64x64 grids and headline +-0.5 % -- profiles/r06/y_*)
-#ifndef PPG_COOP_STORES_FIRST
-#define PPG_COOP_STORES_FIRST 1
-#endif
-    static constexpr bool DYN = PPG_COOP_DYNAMIC && COOP && !FUSED;
+    static constexpr bool DYN = COOP && !FUSED;
 
     // per-lane row fields
     uint32_t xy[T];
@@ -672,10 +660,9 @@ PPG_DEVICE void coop_main(const KParams &P, unsigned char *lds) {
     if (!WALLS && Pc->resident_envs) env.n_resident = (int)wv::first((uint32_t)*Pc->resident_envs);   // (the walls writers keep plain stores)
     // (every wavefront that steps an env writes the whole descriptor table, identical words: it may need it for a mid-step
     // observation long before the workgroup's barrier; a workgroup always has at least one env)
-    if (CoopEnv::DYN) {   // READY bits and tickets start at zero (all wavefronts are still here: this barrier costs nothing)
-        if (w == NW - 1 && ln < CoopEnv::CTL_WORDS - CoopEnv::CTL_READY) ctl[CoopEnv::CTL_READY + ln] = 0u;
-        wv::wg_barrier_lds();
-    }
+    // READY bits and tickets start at zero (all wavefronts are still here: this barrier costs nothing)
+    if (w == NW - 1 && ln < CoopEnv::CTL_WORDS - CoopEnv::CTL_READY) ctl[CoopEnv::CTL_READY + ln] = 0u;
+    wv::wg_barrier_lds();
     if (has_env) env.run_step();
     else if (w < ne && ln == 0) ctl[CoopEnv::CTL_SLOT + 4 * w + 2] = 0xFFFFFFFFu;   // an env slot beyond the batch
 #ifdef PPG_PROFILE_PHASES
@@ -684,18 +671,13 @@ PPG_DEVICE void coop_main(const KParams &P, unsigned char *lds) {
 #else
 #define PPG_COOP_STAMP(i) do { } while (0)
 #endif
-    if (CoopEnv::DYN) {
-        if (w < ne) wv::lds_or(ctl + CoopEnv::CTL_READY, 1u << w);
-        PPG_COOP_STAMP(13);
-#if PPG_COOP_STORES_FIRST
-        if (has_env) env.finish_stores();
-#endif
-        env.coop_write_dynamic(lds);
-    } else {
-        wv::wg_barrier_lds();   // (LDS only: the table stores of this wave need not have reached memory)
-        PPG_COOP_STAMP(13);
-        env.coop_write_all(lds);
-    }
+    if (w < ne) wv::lds_or(ctl + CoopEnv::CTL_READY, 1u << w);
+    PPG_COOP_STAMP(13);
+    // the table stores of a transition wavefront are issued right after its READY bit, before it joins the writing (they need registers
+    // only; with no barrier behind them they delay nobody else and complete under the write phase instead of at the workgroup's tail:
+    // second generation +3.3 %, walls +2.8 %, 64x64 grids and headline +-0.5 % -- profiles/r06/y_*)
+    if (has_env) env.finish_stores();
+    env.coop_write_dynamic(lds);
     PPG_COOP_STAMP(14);
     if (has_env) env.finish_stores();
 }
