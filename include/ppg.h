@@ -709,6 +709,70 @@ int ppg_backward_samples(ppg_handle *h, int32_t n_steps, const double *reward, c
                          const ppg_obs_store *st, const ppg_sample_targets *tg, int32_t values_dtype,
                          double gamma, double lam, void *stream);
 
+/* ---- PPO's clipped loss and its gradients over one minibatch -------------------------------------------------------------
+ * ppg_ppo_loss is the last step of the learner's side: from the columns the calls above stored per sample slot k of ONE species
+ * (action, logp, dist, advantage, value target) and a learner's fresh logits and values for a minibatch of M samples it writes the
+ * gradients of
+ *     L = mean over the valid samples of ( -surr + vf_coeff * vfc - ent_coeff * H + kl_coeff * KL )
+ * (the loss of RLlib's PPOTorchLearner.compute_loss_for_module) with respect to the logits and the values, and per-chunk partial sums
+ * from which the caller composes the loss scalar and its statistics.  Two launches of one-wave workgroups over chunks of
+ * PPG_PPO_CHUNK = 1024 minibatch rows (csrc/ppg_ppo.h), G = ceil(M / 1024); lane l of workgroup g owns rows i = 1024 g + 64 j + l,
+ * j = 0 .. 15 ascending.  No atomics, nothing read back, no library-owned buffer.  All tensors are contiguous device memory.
+ *   Rows     k = index ? index[i] : i.  Row i is VALID when 0 <= k < capacity (compared before k becomes an address), then
+ *            0 <= action[k] < A (compared, never used as an index unchecked) and logp[k] is finite.  Validity is a selection, not a
+ *            multiplication: an invalid row is not counted, adds nothing to any sum, gets +0.0 in grad_logits[i][0..A) and in
+ *            grad_values[i], and nothing else of it is read -- a NaN in its logits row or its other columns reaches no output.
+ *            Among valid rows everything propagates by IEEE rules: a NaN or +inf logit is not masked.
+ *   Launch 1 ppg_ppo_count: workgroup g counts its valid rows (1.0 each, the order below) and stores partial[g][0].
+ *   Launch 2 ppg_ppo_rows: every workgroup adds partial[0..G)[0] in ascending g: n; w = n > 0 ? 1 / n : 0.  Then per valid row, in
+ *            float64, every line one IEEE operation, no fused multiply-add, one rounding to float32 at each store
+ *            (l = logits[i], o = dist[k], a = action[k], sums over the actions in ascending order):
+ *              m = max l_c (a NaN is never the maximum)       d_c = l_c - m        e_c = d_c == -inf ? 0 : exp(d_c)
+ *              s = sum e_c      ls = log(s)      lp_c = d_c - ls      p_c = e_c / s
+ *              (likewise mo, do_c, eo_c, so, lso, lq_c, q_c from o, if dist is given)
+ *              r  = exp(lp_a - (double)logp[k])
+ *              Ad = adv_norm ? ((double)advantage[k] - adv_norm[0]) * adv_norm[1] : (double)advantage[k]
+ *              rc = r < 1 - clip ? 1 - clip : r > 1 + clip ? 1 + clip : r          (1 - clip and 1 + clip formed once in double)
+ *              s1 = Ad * r      s2 = Ad * rc      clipped = s2 < s1      surr = clipped ? s2 : s1      (a tie, and a NaN, is unclipped)
+ *              H  = 0 - sum over c with d_c != -inf of p_c * lp_c            (a masked action's addend is skipped, never 0 * inf)
+ *              KL = sum over c with q_c != 0 of q_c * (lq_c - lp_c)         (+inf where q_c > 0 and the new logit is -inf)
+ *              e  = (double)values[i] - (double)value_target[k]      vf = e * e      over = vf > vf_clip      vfc = over ? vf_clip : vf
+ *              c1 = clipped ? 0 : s1
+ *              g_c = d_c == -inf ? +0.0
+ *                    : w * ( (ent_coeff * (p_c * (lp_c + H)) - c1 * ((c == a ? 1 : 0) - p_c)) + kl_coeff * (p_c - q_c) )
+ *                                                                            (the last term only if dist is given)
+ *              grad_logits[i][c] = (float)g_c       grad_values[i] = (float)(w * (vf_coeff * (over ? 0 : e + e)))
+ *            Without values the value lines are not computed and grad_values is not written; without dist the KL lines are not.
+ *   partial  float64 [G,8]: per workgroup g {n, sum surr, sum vfc, sum vf, sum H, sum KL, sum 1[clipped], sum ((double)logp[k] - lp_a)}
+ *            over its valid rows; columns 2, 3 are +0.0 without values, column 5 without dist.  Each lane keeps its accumulators from
+ *            +0.0 and adds its rows in ascending j; then for m in 1, 2, 4, 8, 16, 32: x = x + x_of_lane(l ^ m) (the order of
+ *            ppg_backward_samples' stats) and lane 0 stores.  Column 0 is written only by launch 1 and columns 1..7 only by launch 2,
+ *            so all G * 8 elements are written and `partial` needs no initial value.  The sum over g and the loss scalar are the
+ *            caller's: one reduction over [G].
+ *   Written  grad_logits [M,A] and grad_values [M] (if given) completely, partial completely; no input is written.
+ * PPG_EINVAL (text in ppg_last_error beginning "ppg_ppo_loss:", nothing is launched): mb NULL; logits, action, logp, advantage,
+ * grad_logits or partial NULL; M < 1 or above INT32_MAX; A outside 1..32; capacity < 0 or above INT32_MAX; only one of values /
+ * value_target set; grad_values without values; kl_coeff != 0 without dist; clip or vf_clip negative or not finite.
+ * The handle supplies the device, the stream ordering and the error text only: no env state is touched.  Asynchronous on `stream`. */
+#define PPG_PPO_CHUNK 1024
+typedef struct ppg_ppo_batch {
+    int64_t M;                  /* minibatch rows, 1 .. INT32_MAX */
+    int64_t capacity;           /* slots of the store columns, 0 .. INT32_MAX */
+    int32_t A;                  /* actions, 1 .. 32 */
+    int32_t reserved_;
+    const int32_t *index;       /* [M] slot of minibatch row i, or NULL: k = i */
+    const float *logits;        /* [M,A] the learner's new logits */
+    const float *values;        /* [M] the critic's new values, or NULL: no value term (value_target must be NULL too) */
+    const int8_t *action;       /* [capacity] */
+    const float *logp;          /* [capacity] */
+    const float *dist;          /* [capacity,A] the behaviour policy's logits, or NULL (kl_coeff must be 0) */
+    const float *advantage;     /* [capacity] */
+    const float *value_target;  /* [capacity] or NULL */
+    const double *adv_norm;     /* DEVICE float64 [2] {shift, scale}, or NULL: the advantage as it is */
+    double clip, vf_clip, vf_coeff, ent_coeff, kl_coeff;
+} ppg_ppo_batch;
+int ppg_ppo_loss(ppg_handle *h, const ppg_ppo_batch *mb, float *grad_logits, float *grad_values, double *partial, void *stream);
+
 /* ---- policy inference next to the env (base_environment/tune_ppo_base_environment.py:106-141) ----------
  * The reference trains two PPO policies (predator_policy / prey_policy) with RLlib's DefaultPPOTorchRLModule and
  * model_config {conv_filters [[16,[3,3],1],[32,[3,3],1],[64,[3,3],1]], fcnet_hiddens [256,256], fcnet_activation relu}.

@@ -24,6 +24,7 @@ OBS_STEP_ON_DEVICE, OBS_F32 = 0x1, 0x2
 ACTION_UNSET = -128
 # flags of ppg_record_logp
 LOGP_STEP_ON_DEVICE = 0x1
+PPO_CHUNK = 1024   # PPG_PPO_CHUNK: minibatch rows per workgroup of ppg_ppo_loss, and per row of its `partial`
 # env_state words
 ENV_WORDS = 20
 (ENV_N_PRED_ROWS, ENV_N_PREY_ROWS, ENV_N_PRED_NEW, ENV_N_PREY_NEW, ENV_NEXT_PRED_ID, ENV_NEXT_PREY_ID,
@@ -156,6 +157,13 @@ class PpgSampleTargets(C.Structure):
     _fields_ = [("values", C.c_void_p * 2), ("advantage", C.c_void_p * 2), ("returns", C.c_void_p * 2), ("stats", C.c_void_p)]
 
 
+class PpgPpoBatch(C.Structure):
+    """include/ppg.h: struct ppg_ppo_batch (one minibatch of one species for ppg_ppo_loss)."""
+    _fields_ = [("M", C.c_int64), ("capacity", C.c_int64), ("A", C.c_int32), ("reserved_", C.c_int32)] + \
+        [(n, C.c_void_p) for n in ("index", "logits", "values", "action", "logp", "dist", "advantage", "value_target", "adv_norm")] + \
+        [(n, C.c_double) for n in ("clip", "vf_clip", "vf_coeff", "ent_coeff", "kl_coeff")]
+
+
 class PpgInitState(C.Structure):
     """include/ppg.h: struct ppg_init_state (host uint16 arrays, cells as (x << 8) | y)."""
     _fields_ = [("pred_xy", C.c_void_p), ("prey_xy", C.c_void_p), ("grass_xy", C.c_void_p), ("episode", C.c_uint32), ("reserved_", C.c_uint32)]
@@ -193,7 +201,7 @@ EXPORTED_SYMBOLS = [
     "ppg_get_wave_plan", "ppg_rebalance", "ppg_set_resident_envs", "ppg_get_resident_envs",
     "ppg_export_grid", "ppg_walls_changed", "ppg_state_bytes", "ppg_export_state", "ppg_import_state", "ppg_pack_bytes", "ppg_pack",
     "ppg_fetch_bytes", "ppg_fetch", "ppg_link", "ppg_record", "ppg_record_obs", "ppg_record_logp", "ppg_backward",
-    "ppg_backward_samples", "ppg_lexkey", "ppg_lds_bytes", "ppg_step_kernel_name", "ppg_last_error",
+    "ppg_backward_samples", "ppg_ppo_loss", "ppg_lexkey", "ppg_lds_bytes", "ppg_step_kernel_name", "ppg_last_error",
 ] + POLICY_SYMBOLS + SPREAD_SYMBOLS
 
 
@@ -271,6 +279,8 @@ def bind(lib: C.CDLL) -> C.CDLL:
     lib.ppg_backward_samples.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,   # handle, n_steps, five inputs
                                          C.POINTER(PpgObsStore), C.POINTER(PpgSampleTargets), C.c_int32, C.c_double, C.c_double,
                                          C.c_void_p]   # st, tg, dtype, gamma, lam, stream
+    lib.ppg_ppo_loss.restype = C.c_int
+    lib.ppg_ppo_loss.argtypes = [C.c_void_p, C.POINTER(PpgPpoBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]   # h, mb, three outputs, stream
     if hasattr(lib, "ppg_alloc_spread"):
         lib.ppg_alloc_spread.restype = C.c_int
         lib.ppg_alloc_spread.argtypes = [C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]

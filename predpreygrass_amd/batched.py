@@ -674,6 +674,55 @@ class BatchedPredPreyGrass:
                                                    float(gamma), float(lam), self._stream(stream)), "ppg_backward_samples")
         return adv, ret, moments
 
+    def ppo_loss(self, logits, action, logp, advantage, index=None, values=None, value_target=None, dist=None, adv_norm=None,
+                 clip=0.3, vf_clip=10.0, vf_coeff=1.0, ent_coeff=0.0, kl_coeff=0.0, stream=None):
+        """The gradients and per-chunk sums of PPO's clipped loss over one minibatch of ONE species, in two launches (`ppg_ppo_loss`,
+        include/ppg.h: validity, the arithmetic line by line, the columns of `partial` and the order of its sums are stated there).
+        logits: float32 [M,A], the learner's new logits, row i for slot `index[i]`; index: int32 [M] or None (slot i); values: float32
+        [M] or None (no value term).  action int8 [capacity], logp float32 [capacity], dist float32 [capacity,A] or None, advantage
+        float32 [>= capacity], value_target float32 [>= capacity] (given exactly when values is): the columns of a sample store and of
+        backward_samples(); `capacity` is action's length.  adv_norm: float64 [2] {shift, scale} on the device or None.
+        Returns (grad_logits float32 [M,A], grad_values float32 [M] or None, partial float64 [ceil(M / 1024), 8]), newly allocated and
+        written completely; `partial.sum(0)` = {n, sum surr, sum vfc, sum vf, sum H, sum KL, clipped rows, sum (logp_old - logp_new)}
+        over the valid rows.  The env's state is not touched.
+        stream (optional): as in backward() -- the launches and the allocation of the outputs go to that stream."""
+        f32 = (torch.float32,)
+        if logits.dim() != 2 or logits.shape[0] < 1 or not 1 <= logits.shape[1] <= 32:
+            raise ValueError(f"logits must be [M,A] with M >= 1 and A in 1..32, not {tuple(logits.shape)}")
+        M, A = (int(n) for n in logits.shape)
+        mb = _abi.PpgPpoBatch()
+        mb.M, mb.A = M, A
+        mb.logits = anchor = self._tensor_arg("logits", logits, f32, (M, A)).value
+        if index is not None:
+            if not isinstance(index, torch.Tensor) or index.dtype != torch.int32:
+                raise ValueError(f"index must have dtype=torch.int32 (the slot words of the store), not {getattr(index, 'dtype', type(index))}")
+            mb.index = self._tensor_arg("index", index, (torch.int32,), (M,)).value
+        if (values is None) != (value_target is None):
+            raise ValueError("values and value_target come together: both tensors, or both None")
+        if values is not None:
+            mb.values = self._tensor_arg("values", values, f32, (M,)).value
+        if action.dim() != 1:
+            raise ValueError(f"action must be [capacity], not {tuple(action.shape)}")
+        capacity = mb.capacity = int(action.shape[0])
+        mb.action = self._rows_arg("action", action, (torch.int8,), (), capacity, anchor)
+        mb.logp = self._rows_arg("logp", logp, f32, (), capacity, anchor, "elements")
+        if dist is not None:
+            mb.dist = self._rows_arg("dist", dist, f32, (A,), capacity, anchor)
+        mb.advantage = self._rows_arg("advantage", advantage, f32, (), capacity, anchor, "elements")
+        if value_target is not None:
+            mb.value_target = self._rows_arg("value_target", value_target, f32, (), capacity, anchor, "elements")
+        if adv_norm is not None:
+            mb.adv_norm = self._tensor_arg("adv_norm", adv_norm, (torch.float64,), (2,)).value
+        mb.clip, mb.vf_clip, mb.vf_coeff, mb.ent_coeff, mb.kl_coeff = (float(x) for x in (clip, vf_clip, vf_coeff, ent_coeff, kl_coeff))
+        G = (M + _abi.PPO_CHUNK - 1) // _abi.PPO_CHUNK
+        grad_logits, grad_values, partial = _alloc_on(self.device, stream, lambda: (
+            torch.empty((M, A), dtype=torch.float32, device=self.device),
+            torch.empty((M,), dtype=torch.float32, device=self.device) if values is not None else None,
+            torch.empty((G, 8), dtype=torch.float64, device=self.device)))
+        self._check(self._lib.ppg_ppo_loss(self._handle, C.byref(mb), _ptr(grad_logits), _ptr(grad_values), _ptr(partial),
+                                           self._stream(stream)), "ppg_ppo_loss", value_error=True)
+        return grad_logits, grad_values, partial
+
     def export_grid(self):
         """grid_world_state of every env: float64 [B,4,G,G] (predpreygrass_rllib_env.py:124)."""
         G = self.grid_size

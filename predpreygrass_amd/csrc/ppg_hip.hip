@@ -237,8 +237,8 @@ static int backend_rebalance(ppg_handle *h, int weight_pred, int weight_prey, vo
 }
 
 // ---- the learner-side kernels: one wavefront per workgroup, the parameter block by value ----------------------------------------
-// ppg_pack / ppg_fetch / ppg_link / ppg_record / ppg_record_obs / ppg_record_logp / ppg_backward / ppg_backward_samples (ppg_pack.h,
-// ppg_fetch.h, ppg_link.h, ppg_record.h, ppg_obs_store.h, ppg_logp.h, ppg_backward.h)
+// ppg_pack / ppg_fetch / ppg_link / ppg_record / ppg_record_obs / ppg_record_logp / ppg_backward / ppg_backward_samples / ppg_ppo_loss
+// (ppg_pack.h, ppg_fetch.h, ppg_link.h, ppg_record.h, ppg_obs_store.h, ppg_logp.h, ppg_backward.h, ppg_ppo.h)
 #define PPG_ROWS_KERNEL(name, Params, main, lds_bytes)                                         \
     extern "C" __global__ void __launch_bounds__(64) name(const ppg::Params K) {              \
         __shared__ __attribute__((aligned(16))) unsigned char lds[lds_bytes];                  \
@@ -257,6 +257,8 @@ PPG_ROWS_KERNEL(ppg_logp_scan, LogpParams, logp_scan_main, ppg::ROWS_SCAN_LDS_BY
 PPG_ROWS_KERNEL_NO_LDS(ppg_logp_rows, LogpParams, logp_rows_main)
 PPG_ROWS_KERNEL(ppg_backward_rows, BackwardParams, backward_main, ppg::BACKWARD_LDS_BYTES)
 PPG_ROWS_KERNEL(ppg_backward_samples_rows, BackwardSamplesParams, backward_samples_main, ppg::BACKWARD_LDS_BYTES)
+PPG_ROWS_KERNEL_NO_LDS(ppg_ppo_count, PpoParams, ppo_count_main)
+PPG_ROWS_KERNEL(ppg_ppo_rows, PpoParams, ppo_rows_main, ppg::PPO_LDS_BYTES)
 
 // `grid` one-wave workgroups of `kernel` on `stream`
 template <class Params>
@@ -285,6 +287,10 @@ static int backend_record_logp(ppg_handle *h, const ppg::LogpParams &K, void *st
 static int backend_backward(ppg_handle *h, const ppg::BackwardParams &K, void *stream) { return backend_launch_rows(h, ppg_backward_rows, K.batch, K, stream); }
 static int backend_backward_samples(ppg_handle *h, const ppg::BackwardSamplesParams &K, void *stream) {
     return backend_launch_rows(h, ppg_backward_samples_rows, K.batch, K, stream);
+}
+static int backend_ppo_loss(ppg_handle *h, const ppg::PpoParams &K, void *stream) {
+    if (int rc = backend_launch_rows(h, ppg_ppo_count, K.G, K, stream)) return rc;
+    return backend_launch_rows(h, ppg_ppo_rows, K.G, K, stream);
 }
 
 static int backend_copy(ppg_handle *h, void *dst, const void *src, size_t bytes, bool to_device, void *stream) {

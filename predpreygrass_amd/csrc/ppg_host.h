@@ -24,6 +24,7 @@
 #include "ppg_backward.h"
 #include "ppg_obs_store.h"
 #include "ppg_logp.h"
+#include "ppg_ppo.h"
 
 // How a handle's step is scheduled (never what it computes): wavefronts per workgroup, the row count from which helper wavefronts
 // stay, and -- cooperative kernels -- how many envs share a workgroup (0 = one env per workgroup, the ppg[w]_step kernels).
@@ -545,15 +546,16 @@ static int backend_pack(ppg_handle *h, const ppg::PackParams &K, void *stream);
 static int backend_fetch(ppg_handle *h, const ppg::FetchParams &K, void *stream);
 static void backend_free(ppg_handle *h, void *p);
 // the launches of ppg_link (ppg_link.h), ppg_record (ppg_record.h), ppg_record_obs (ppg_obs_store.h: two), ppg_record_logp
-// (ppg_logp.h: two), ppg_backward and ppg_backward_samples (ppg_backward.h)
+// (ppg_logp.h: two), ppg_backward and ppg_backward_samples (ppg_backward.h), ppg_ppo_loss (ppg_ppo.h: two)
 static int backend_link(ppg_handle *h, const ppg::LinkParams &K, void *stream);
 static int backend_record(ppg_handle *h, const ppg::RecordParams &K, void *stream);
 static int backend_record_obs(ppg_handle *h, const ppg::ObsStoreParams &K, void *stream);
 static int backend_record_logp(ppg_handle *h, const ppg::LogpParams &K, void *stream);
 static int backend_backward(ppg_handle *h, const ppg::BackwardParams &K, void *stream);
 static int backend_backward_samples(ppg_handle *h, const ppg::BackwardSamplesParams &K, void *stream);
+static int backend_ppo_loss(ppg_handle *h, const ppg::PpoParams &K, void *stream);
 #ifdef PPG_WAVE_EMU
-// CPU test build (tests/wave_emu): `grid` one-wave workgroups of Main with exactly LDS bytes each, as on the device.  These six
+// CPU test build (tests/wave_emu): `grid` one-wave workgroups of Main with exactly LDS bytes each, as on the device.  These seven
 // launches stand here, not next to the test backend's backend_pack / backend_fetch: a revision's test suite is also run against
 // the sources of the revision after it, and its tests/wave_emu/ppg_emu.cpp defines only the launches that existed when it was written.
 template <class P, void (*Main)(const P &, unsigned char *), int LDS>
@@ -584,6 +586,10 @@ static int backend_backward(ppg_handle *, const ppg::BackwardParams &K, void *) 
 }
 static int backend_backward_samples(ppg_handle *, const ppg::BackwardSamplesParams &K, void *) {
     return ppg_emu_rows<ppg::BackwardSamplesParams, ppg::backward_samples_main, ppg::BACKWARD_LDS_BYTES>(K, K.batch);
+}
+static int backend_ppo_loss(ppg_handle *, const ppg::PpoParams &K, void *) {
+    ppg_emu_rows<ppg::PpoParams, ppg::ppo_count_main>(K, K.G);
+    return ppg_emu_rows<ppg::PpoParams, ppg::ppo_rows_main, ppg::PPO_LDS_BYTES>(K, K.G);
 }
 #endif
 
@@ -1422,6 +1428,35 @@ int ppg_backward_samples(ppg_handle *h, int32_t n_steps, const double *reward, c
     K.gamma = gamma; K.gl = gamma * lam;
     K.stats = tg->stats;
     return backend_backward_samples(h, K, stream);
+}
+
+int ppg_ppo_loss(ppg_handle *h, const ppg_ppo_batch *mb, float *grad_logits, float *grad_values, double *partial, void *stream) {
+    if (!h) return PPG_EINVAL;
+    if (!mb) return ppg_fail(h, PPG_EINVAL, "ppg_ppo_loss: mb is NULL");
+    if (!mb->logits || !mb->action || !mb->logp || !mb->advantage)
+        return ppg_fail(h, PPG_EINVAL, "ppg_ppo_loss: logits, action, logp or advantage of ppg_ppo_batch is NULL");
+    if (!grad_logits || !partial) return ppg_fail(h, PPG_EINVAL, "ppg_ppo_loss: grad_logits or partial is NULL");
+    if (mb->M < 1 || mb->M > INT32_MAX) return ppg_fail(h, PPG_EINVAL, "ppg_ppo_loss: M = %lld outside [1, INT32_MAX]", (long long)mb->M);
+    if (mb->A < 1 || mb->A > ppg::PPO_MAX_ACTIONS) return ppg_fail(h, PPG_EINVAL, "ppg_ppo_loss: A = %d outside 1..32", mb->A);
+    if (mb->capacity < 0 || mb->capacity > INT32_MAX)
+        return ppg_fail(h, PPG_EINVAL, "ppg_ppo_loss: capacity = %lld outside [0, INT32_MAX]", (long long)mb->capacity);
+    if (!mb->values != !mb->value_target) return ppg_fail(h, PPG_EINVAL, "ppg_ppo_loss: only one of values and value_target is set");
+    if (grad_values && !mb->values) return ppg_fail(h, PPG_EINVAL, "ppg_ppo_loss: grad_values without values");
+    if (mb->kl_coeff != 0.0 && !mb->dist) return ppg_fail(h, PPG_EINVAL, "ppg_ppo_loss: kl_coeff != 0 needs dist");
+    if (!(mb->clip >= 0.0 && mb->clip < INFINITY)) return ppg_fail(h, PPG_EINVAL, "ppg_ppo_loss: clip = %g is negative or not finite", mb->clip);
+    if (!(mb->vf_clip >= 0.0 && mb->vf_clip < INFINITY))
+        return ppg_fail(h, PPG_EINVAL, "ppg_ppo_loss: vf_clip = %g is negative or not finite", mb->vf_clip);
+    ppg::PpoParams K;
+    memset(&K, 0, sizeof K);
+    K.M = mb->M; K.capacity = mb->capacity; K.A = mb->A;
+    K.G = (int32_t)((mb->M + ppg::PPO_CHUNK - 1) / ppg::PPO_CHUNK);
+    K.index = mb->index; K.logits = mb->logits; K.values = mb->values;
+    K.action = mb->action; K.logp = mb->logp; K.dist = mb->dist; K.advantage = mb->advantage; K.value_target = mb->value_target;
+    K.adv_norm = mb->adv_norm;
+    K.clip_lo = 1.0 - mb->clip; K.clip_hi = 1.0 + mb->clip;
+    K.vf_clip = mb->vf_clip; K.vf_coeff = mb->vf_coeff; K.ent_coeff = mb->ent_coeff; K.kl_coeff = mb->kl_coeff;
+    K.grad_logits = grad_logits; K.grad_values = grad_values; K.partial = partial;
+    return backend_ppo_loss(h, K, stream);
 }
 
 #ifdef PPG_PROFILE_PHASES

@@ -85,6 +85,18 @@ the bits of scatter() -> returns_and_gae() -> flat() -> .float() (kept verbatim 
     adv, ret, stats = traj.targets(v_pred, v_prey, 0.99, 0.95)      # adv[s], ret[s]: float32 [n_s] in the order of samples(s)
     count, mean, std = traj.advantage_moments(stats)                # float64 [2] each, no read-back
     adv_n = (adv[PREY] - mean[PREY]) / (std[PREY] + 1e-8)           # the usual value target: adv[PREY] + v_prey
+
+and the minibatch step of the learner closes the loop: PPO's clipped loss (RLlib's `compute_loss_for_module`) and its gradients from those
+columns and the learner's fresh logits and values, in two launches (`env.ppo_loss()`, `ppg_ppo_loss`, csrc/ppg_ppo.h), nothing read back:
+
+    norm = traj.advantage_norm(stats)                               # float64 [2,2]: {mean, 1 / (std + eps)} per species
+    index = torch.randperm(n_prey, device=dev).to(torch.int32)[:128]          # slots of a minibatch
+    logits, values = prey_net(obs[index.long()])
+    loss, st, grad_logits, grad_values = traj.ppo_loss(PREY, logits, values, index, adv[PREY], ret[PREY], adv_norm=norm)
+    torch.autograd.backward([logits, values], [grad_logits, grad_values]); optimizer.step()
+
+Samples whose action is still ACTION_UNSET or whose logp is still NaN are skipped, so an index over all slots is legal.
+`ppo_loss_function()` is the same behind `loss.backward()`, `ppo_loss_torch()` the same loss as torch ops.
 """
 from __future__ import annotations
 
@@ -534,6 +546,170 @@ class AgentTrajectories:
         mean = total[:, 1] / n
         var = (total[:, 2] / n - mean * mean).clamp_min(0.0)
         return count, mean, var.sqrt()
+
+    @staticmethod
+    def advantage_norm(stats, eps=1e-8):
+        """float64 [2,2] on the device, per species {mean, 1 / (std + eps)} from the `stats` of targets() (advantage_moments(), nothing
+        read back): row s is the `adv_norm` of ppo_loss(s, ...), which then uses (A - mean) / (std + eps) as the advantage."""
+        _, mean, std = AgentTrajectories.advantage_moments(stats)
+        return torch.stack((mean, 1.0 / (std + eps)), dim=1).contiguous()
+
+    _PPO_STATS = ("n", "policy_loss", "vf_loss", "vf_loss_unclipped", "entropy", "kl", "clip_fraction", "approx_kl")
+
+    def _ppo_columns(self, species, advantage, value_target, values, index, adv_norm, kl_coeff):
+        """What ppo_loss() and ppo_loss_torch() take from the store for n = len(advantage) samples: (action[:n], logp[:n], dist[:n] or
+        None, the species' adv_norm [2] or None); ValueError for what both refuse."""
+        self._need_store("ppo_loss", logp=True)
+        st = self.store
+        if st.action is None:
+            raise RuntimeError("ppo_loss() needs a store that keeps actions")
+        if index is not None and (not isinstance(index, torch.Tensor) or index.dtype != torch.int32):
+            raise ValueError(f"index must have dtype=torch.int32 (the slot numbers of the store), not {getattr(index, 'dtype', type(index))}")
+        if advantage.dim() != 1 or advantage.shape[0] > st.capacity[species]:
+            raise ValueError(f"advantage must be [n] with n <= the store's {st.capacity[species]} rows, not {tuple(advantage.shape)}")
+        if (values is None) != (value_target is None):
+            raise ValueError("values and value_target come together: both tensors, or both None")
+        if kl_coeff != 0 and st.dist is None:
+            raise ValueError("kl_coeff != 0 needs the behaviour policy's logits: AgentTrajectories(..., dist=True)")
+        if adv_norm is not None:
+            if tuple(adv_norm.shape) == (2, 2):
+                adv_norm = adv_norm[species]
+            if tuple(adv_norm.shape) != (2,) or adv_norm.dtype != torch.float64:
+                raise ValueError(f"adv_norm must be a float64 tensor [2] or [2,2] (advantage_norm()), not {adv_norm.dtype} {list(adv_norm.shape)}")
+        n = advantage.shape[0]
+        return st.action[species][:n], st.logp[species][:n], None if st.dist is None else st.dist[species][:n], adv_norm
+
+    def ppo_loss(self, species, logits, values, index, advantage, value_target, *, clip=0.3, vf_clip=10.0, vf_coeff=1.0, ent_coeff=0.0,
+                 kl_coeff=0.2, adv_norm=None):
+        """(loss, stats, grad_logits, grad_values): PPO's clipped loss of one minibatch of one species -- the mean over the valid
+        samples of -min(A r, A clamp(r, 1 - clip, 1 + clip)) + vf_coeff min((v - target)^2, vf_clip) - ent_coeff H + kl_coeff
+        KL(old || new), RLlib's `PPOTorchLearner.compute_loss_for_module` -- and its gradients, in two launches (`env.ppo_loss()`,
+        `ppg_ppo_loss`, csrc/ppg_ppo.h: float64 arithmetic rounded once at the stores), nothing read back.
+        logits float32 [M,A] and values float32 [M] (or None: no value term): the learner's outputs for the samples in slots `index`,
+        int32 [M] (None: slots 0 .. M - 1); advantage, value_target: float32 [n] in sample order (targets(); value_target None exactly
+        when values is); adv_norm: advantage_norm(stats) or its row.  `action`, `logp` and `dist` come from the store; a sample whose
+        slot is outside [0, n), whose action is still ACTION_UNSET or whose logp is still NaN (the last step's, until a further
+        record_policy()) is skipped: not counted, gradient +0.0.
+        stats: 0-dim float64 device tensors n, policy_loss, vf_loss, vf_loss_unclipped, entropy, kl, clip_fraction, approx_kl (means
+        over the valid samples; with n = 0 all 0), and loss = policy_loss + vf_coeff vf_loss - ent_coeff entropy + kl_coeff kl, composed
+        from `partial.sum(0)` with torch ops.  grad_logits [M,A] / grad_values [M] ARE d loss / d logits and d loss / d values, so the
+        backward pass that costs nothing more is
+            torch.autograd.backward([logits, values], [grad_logits, grad_values])
+        in front of optimizer.step(); `ppo_loss_function()` wraps the same call for `loss.backward()`."""
+        action, logp, dist, adv_norm = self._ppo_columns(species, advantage, value_target, values, index, adv_norm, kl_coeff)
+        grad_logits, grad_values, partial = self.env.ppo_loss(
+            logits.detach(), action, logp, advantage, index=index, values=None if values is None else values.detach(),
+            value_target=value_target, dist=dist, adv_norm=adv_norm, clip=clip, vf_clip=vf_clip, vf_coeff=vf_coeff, ent_coeff=ent_coeff,
+            kl_coeff=kl_coeff)
+        total = partial.sum(0)
+        n = total[0]
+        mean = total[1:] / n.clamp_min(1.0)
+        stats = dict(zip(self._PPO_STATS, (n, -mean[0], *mean[1:].unbind(0))))
+        return _ppo_compose(stats, vf_coeff, ent_coeff, kl_coeff, values is not None), stats, grad_logits, grad_values
+
+    def ppo_loss_torch(self, species, logits, values, index, advantage, value_target, *, clip=0.3, vf_clip=10.0, vf_coeff=1.0,
+                       ent_coeff=0.0, kl_coeff=0.2, adv_norm=None, dtype=torch.float32):
+        """(loss, stats) of ppo_loss() as plain differentiable torch ops in `dtype` -- RLlib's formulas spelled out: log_softmax, the
+        gather at the action, exp, clamp, min, the entropy and the KL of two categoricals, the clipped squared error, and a mean over
+        the valid samples (the others are selected away in front of every op, so that they neither count nor put a NaN into a
+        gradient) -- some forty small launches and a dozen [M,A] temporaries, and as many again for `loss.backward()` (timing
+        baseline, cross-check, fallback)."""
+        action, logp, dist, adv_norm = self._ppo_columns(species, advantage, value_target, values, index, adv_norm, kl_coeff)
+        M, A = logits.shape
+        n = advantage.shape[0]
+        k = torch.arange(M, device=logits.device) if index is None else index.long()
+        inside = (k >= 0) & (k < n)
+        k = torch.where(inside, k, torch.zeros_like(k))
+        if n == 0:
+            act, lp_old = torch.full((M,), -1, device=logits.device), torch.full((M,), float("nan"), dtype=dtype, device=logits.device)
+        else:
+            act, lp_old = action[k].long(), logp[k].to(dtype)
+        valid = inside & (act >= 0) & (act < A) & torch.isfinite(lp_old)
+        pick = lambda x, fill=0.0: torch.where(valid, x, torch.full_like(x, fill))
+        count = valid.sum().to(dtype)
+        denom = count.clamp_min(1.0)
+        masked_mean = lambda x: pick(x).sum() / denom
+
+        def log_probs(raw):
+            raw = torch.where(valid[:, None], raw.to(dtype), torch.zeros((), dtype=dtype, device=raw.device))
+            lp = torch.log_softmax(raw, dim=1)
+            finite = lp > float("-inf")
+            return lp, torch.where(finite, lp, torch.zeros_like(lp)), lp.exp()
+        lp, lp_safe, p = log_probs(logits)
+        act = pick(act, 0)
+        lp_a = lp.gather(1, act[:, None])[:, 0]
+        adv = advantage.to(dtype)[k] if n else torch.zeros((M,), dtype=dtype, device=logits.device)
+        if adv_norm is not None:
+            adv = (adv - adv_norm[0].to(dtype)) * adv_norm[1].to(dtype)
+        adv, lp_old = pick(adv), pick(lp_old)
+        ratio = (lp_a - lp_old).exp()
+        s1, s2 = adv * ratio, adv * ratio.clamp(1.0 - clip, 1.0 + clip)
+        surrogate = torch.min(s1, s2)
+        entropy = -(p * lp_safe).sum(1)
+        zero = torch.zeros((), dtype=dtype, device=logits.device)
+        kl = vf = vfc = None
+        if dist is not None and n:
+            lq, lq_safe, q = log_probs(dist[k])
+            kl = torch.where(q > 0, q * (lq_safe - lp), torch.zeros_like(q)).sum(1)
+        if values is not None:
+            target = value_target.to(dtype)[k] if n else torch.zeros((M,), dtype=dtype, device=logits.device)
+            vf = (pick(values.to(dtype)) - pick(target)) ** 2
+            vfc = vf.clamp(0.0, vf_clip)
+        stats = {"n": count, "policy_loss": -masked_mean(surrogate), "vf_loss": zero if vfc is None else masked_mean(vfc),
+                 "vf_loss_unclipped": zero if vf is None else masked_mean(vf), "entropy": masked_mean(entropy),
+                 "kl": zero if kl is None else masked_mean(kl), "clip_fraction": masked_mean((s2 < s1).to(dtype)),
+                 "approx_kl": masked_mean(lp_old - lp_a)}
+        return _ppo_compose(stats, vf_coeff, ent_coeff, kl_coeff, values is not None), stats
+
+
+def _ppo_compose(stats, vf_coeff, ent_coeff, kl_coeff, has_values):
+    """The loss scalar from the means: a term whose coefficient is 0 is left out, not multiplied by 0 (an infinite KL that is not
+    optimised against does not make the loss NaN)."""
+    loss = stats["policy_loss"]
+    if has_values and vf_coeff != 0:
+        loss = loss + vf_coeff * stats["vf_loss"]
+    if ent_coeff != 0:
+        loss = loss - ent_coeff * stats["entropy"]
+    if kl_coeff != 0:
+        loss = loss + kl_coeff * stats["kl"]
+    return loss
+
+
+class _PpoLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, values, traj, species, index, advantage, value_target, kw):
+        loss, stats, grad_logits, grad_values = traj.ppo_loss(species, logits, values, index, advantage, value_target, **kw)
+        ctx.save_for_backward(grad_logits, *(() if grad_values is None else (grad_values,)))
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        saved = ctx.saved_tensors
+        scale = grad_output.to(torch.float32)
+        return (saved[0] * scale, saved[1] * scale if len(saved) > 1 else None) + (None,) * 6
+
+
+def ppo_loss_function(traj, species, logits, values, index, advantage, value_target, **kw):
+    """`traj.ppo_loss(...)` as a `torch.autograd.Function`: returns (loss, stats) with `loss` attached to `logits` and `values`, so that
+    `loss.backward()` (or a sum of both species' losses) works as with ppo_loss_torch().  The gradients were computed by the forward
+    call; backward multiplies the stored grad_logits / grad_values by `grad_output`, ONE elementwise op per tensor -- what
+    `torch.autograd.backward([logits, values], [grad_logits, grad_values])` on ppo_loss()'s own outputs saves.  Keyword arguments: those
+    of ppo_loss()."""
+    out = {}
+    loss = _PpoLoss.apply(logits, values, _StatsSink(traj, out), species, index, advantage, value_target, kw)
+    return loss, out["stats"]
+
+
+class _StatsSink:
+    """Hands ppo_loss()'s stats out of the autograd Function's forward (which can only return tensors that take part in the graph)."""
+
+    def __init__(self, traj, out):
+        self.traj, self.out = traj, out
+
+    def ppo_loss(self, *args, **kw):
+        result = self.traj.ppo_loss(*args, **kw)
+        self.out["stats"] = result[1]
+        return result
 
 
 class GraphedCollector:
