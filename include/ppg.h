@@ -883,6 +883,46 @@ int ppg_policy_describe(const ppg_policy_spec *spec, int32_t *out, int32_t n);
                                    * cells fall into all LDS bank groups (csrc/ppg_policy.h: ppg_slot_table) */
 int ppg_policy_pack(const ppg_policy_spec *spec, int32_t what, uint16_t *out, uint64_t capacity, uint64_t *n_words);
 
+/* New weights for a policy that exists, from the DEVICE: the learner-to-actor hand-over without the host.  The weight pointers of
+ * `spec` are DEVICE pointers on p's device -- float32, contiguous, PyTorch layouts, e.g. the parameters an optimiser has just stepped
+ * -- and its shape must be the one `p` was created with: a difference in obs_channels, obs_range, n_actions, layout, flatten, n_conv,
+ * conv_out[], n_fc or fc_out[] is PPG_EINVAL with a message that names the field; so are a NULL p, a NULL spec and a NULL weight
+ * pointer of a layer the shape has.  One kernel (csrc/ppg_policy.h: ppg_policy_repack) gathers the parameters through a repack map
+ * into the fragment order and writes them INTO THE POLICY'S EXISTING WEIGHT IMAGE, to the bits ppg_policy_create_spec would have
+ * uploaded for them: no address the policy kernels read changes, so a hipGraph captured around ppg_policy_act earlier acts with the new
+ * weights at its next replay.  The FIRST update of a policy builds the map, allocates it on the device and uploads it -- that call may
+ * block and must not stand inside a stream capture; the map is freed by ppg_policy_destroy.  Every LATER update only launches: no
+ * allocation, no host wait, no copy; asynchronous on `stream` and legal inside a stream capture (the parameters are read when the
+ * kernel RUNS, so a captured update picks up whatever they hold at each replay).
+ * ORDER: an update is ordered like an act.  Put it on a stream behind the last ppg_policy_act that should see the old weights and in
+ * front of the first that should see the new ones, and behind whatever wrote the parameters.  The two-species ppg_policy_act forks
+ * its side stream from `stream` and joins back into it, so same-stream order is enough.
+ * Non-finite parameters are carried as non-finite, with unspecified bit patterns. */
+int ppg_policy_update(ppg_policy *p, const ppg_policy_spec *spec, void *stream);
+
+/* The byte image of a network's weights as ppg_policy_create_spec uploads it -- computed without a device, like ppg_policy_pack, so that
+ * ppg_policy_update's map can be checked on the CPU.  The image: eleven arrays one behind the other, each padded with zeros to a
+ * multiple of 256 bytes -- the convolutions 0-5, three arrays of the linear layers (a network without hidden head layers: the head,
+ * the head per wavefront, nothing), PPG_POLICY_PACK_CONV1X's, PPG_POLICY_PACK_SLOTS' (with the kernels PPG_POLICY_PIPE picks: see
+ * ppg_policy_describe) -- then 560 floats of biases.  what:
+ *   PPG_POLICY_IMAGE_PACKED    the image, from the host weights of `spec`
+ *   PPG_POLICY_IMAGE_REPACKED  the same bytes made the update's way: a buffer filled with 0xA5 that holds nothing but the slot table's
+ *                              array, then the map and the word function of ppg_policy_update run on the CPU over the host weights
+ *   PPG_POLICY_IMAGE_MAP       the map itself, int32 words (the weight pointers of `spec` are not read): a header of 32 words --
+ *                              [0] 32, [1] W = bf16 words covered = image bytes [0, 2 W), every array in front of the slot table,
+ *                              [2] floats of the bias block, [3] bytes of the image, [4] byte offset of the bias block, [5 + l] byte
+ *                              offset of array l, [16 + l] bf16 words of array l (l < 11) -- then W entries, one per bf16 word from
+ *                              image byte 0 on, then one per float of the bias block.  An entry: 0 = the constant zero; otherwise
+ *                              bits 24-28 = 1 + tensor (conv_w[0..5] 0-5, conv_b[0..5] 6-11, fc_w[0..2] 12-14, fc_b[0..2] 15-17), bits
+ *                              0-23 = the element of that tensor, bit 29 set = not the element b itself but what bfloat16 leaves of
+ *                              it, b - float(bf16(b)) (the second word of a convolution's bias).  Weight entries are rounded to
+ *                              bfloat16 (to nearest even, in integer arithmetic), bias entries are copied.
+ * *n_bytes = bytes of the result; out == NULL or capacity (bytes) too small: only the size is reported (PPG_OK). */
+#define PPG_POLICY_IMAGE_PACKED 0
+#define PPG_POLICY_IMAGE_REPACKED 1
+#define PPG_POLICY_IMAGE_MAP 2
+int ppg_policy_image(const ppg_policy_spec *spec, int32_t what, void *out, uint64_t capacity, uint64_t *n_bytes);
+
 /* A device buffer for the caller-owned observation tensors whose physical pages are picked at random from a stretch of device
  * memory `spread` times its size (HIP virtual memory management: spread x as many 2 MB chunks are created, a random subset is
  * mapped in random order, the rest is given back at once).  Optional -- any device pointer works as obs_pred / obs_prey -- but where

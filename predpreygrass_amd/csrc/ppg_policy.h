@@ -37,6 +37,8 @@
 #include <type_traits>
 #include <vector>
 
+#include "ppg_policy_pack.h"
+
 namespace ppgpol {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -973,6 +975,43 @@ PPG_POLICY_KERNEL(ppg_policy_forward_hwc16_f64, 0, 16)   // channels-last, 9 <= 
 PPG_POLICY_KERNEL(ppg_policy_forward_hwc16_f32, 1, 16)
 PPG_POLICY_KERNEL(ppg_policy_forward_hwc16_bf16, 2, 16)
 
+// ---- ppg_policy_update: float32 parameters in device memory -> the weight image, through the repack map (ppg_policy_pack.h) ----
+// One launch per policy, grid-stride over the image's 16-byte units of eight bf16 words and, behind them, the floats of the bias block.
+// A lane reads its unit's eight map entries (two 16-byte loads), gathers the eight parameters they name and writes the unit with one
+// 16-byte store.  The table of source pointers is read in place from the kernarg segment (indexed per lane: by value it would be a
+// private array).  No atomics, no LDS; latency-bound: a few dependent loads per lane, about a thousand workgroups for the largest image.
+struct RepackParams {
+    const float *src[PPG_SRC_N];   // DEVICE pointers (PPG_SRC_*); those of layers the shape does not have are in no map entry and never read
+    const int32_t *map;            // [8 n_units + n_bias] entries (the map behind its header)
+    u32x4_t *image;                // dev_weights: n_units units from its first byte on
+    float *bias;                   // the bias block inside dev_weights
+    uint32_t n_units, n_bias;
+};
+typedef int32_t i32x4_t __attribute__((ext_vector_type(4)));
+extern "C" __global__ void __launch_bounds__(256) ppg_policy_repack(const RepackParams K) {
+    const auto *Kp = (const __attribute__((address_space(4))) RepackParams *)__builtin_amdgcn_kernarg_segment_ptr();
+    const float *const __attribute__((address_space(4))) *src = Kp->src;
+    const uint32_t n = K.n_units + K.n_bias, stride = gridDim.x * 256u;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += stride) {
+        if (i < K.n_units) {
+            const GLOBAL_AS i32x4_t *m = (const GLOBAL_AS i32x4_t *)K.map + 2 * (size_t)i;
+            const i32x4_t e0 = m[0], e1 = m[1];
+            const int32_t e[8] = {e0[0], e0[1], e0[2], e0[3], e1[0], e1[1], e1[2], e1[3]};
+            float f[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] = ppg_repack_fetch(e[j], src);   // (eight independent gathers, all in flight)
+            u32x4_t v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                v[j] = (uint32_t)ppg_bf16_bits(ppg_repack_finish(e[2 * j], f[2 * j])) | (uint32_t)ppg_bf16_bits(ppg_repack_finish(e[2 * j + 1], f[2 * j + 1])) << 16;
+            *((GLOBAL_AS u32x4_t *)K.image + i) = v;
+        } else {
+            const uint32_t k = i - K.n_units;
+            K.bias[k] = ppg_repack_value(K.map[8 * (size_t)K.n_units + k], src);
+        }
+    }
+}
+
 }  // namespace ppgpol
 
 #include "ppg_policy_direct.h"
@@ -1002,6 +1041,12 @@ struct ppg_policy {
     int32_t lds_bytes;
     hipStream_t side;      // ppg_policy_act with both species: the predators' launch runs beside the prey's (fork / join by events)
     hipEvent_t fork, join;
+    // ppg_policy_update: the shape the policy was created with (weight pointers NULL), where each array lies in dev_weights, and the
+    // repack map on the device (allocated by the first update, freed by ppg_policy_destroy)
+    ppg_policy_spec shape;
+    ppg_policy_image_layout image;
+    int32_t *map_dev;
+    int32_t cus;
     char err[256];
 };
 
@@ -1027,95 +1072,6 @@ static int ppg_policy_mirror(const ppg_policy *p, int rc) {
         hipError_t e_ = (call);                                                                           \
         if (e_ != hipSuccess) return ppg_policy_fail(p, PPG_EHIP, "%s: %s", #call, hipGetErrorString(e_)); \
     } while (0)
-
-// MFMA row r of a 32-row tile computes this feature of the tile (see ORIENTATION above)
-static int ppg_row_feature(int r) { return 16 * ((r >> 2) & 1) + 4 * (r >> 3) + (r & 3); }
-
-static uint16_t ppg_bf16_bits(float f) {   // round to nearest even (finite weights)
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40u);
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-
-// conv weights [cout][cin][3][3] -> fragments [mt][ks][lane][8]: lane (r = lane & 31, h = lane >> 5) holds, for K block
-// q = 2 ks + h = tap * CBIN + cb, the eight input channels 8 cb .. 8 cb + 7 of output channel 32 mt + r at tap (ky, kx)
-static void ppg_pack_conv(const float *w, const float *bias, int cout, int cin, int cbin, int mt_n, std::vector<uint16_t> &out) {
-    const int Q = 9 * cbin, KS = (Q + 2) / 2;   // (block Q = the bias, ConvW)
-    out.assign((size_t)mt_n * KS * 64 * 8, 0);
-    for (int mt = 0; mt < mt_n; ++mt)
-        for (int ks = 0; ks < KS; ++ks)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int r = lane & 31, h = lane >> 5, q = 2 * ks + h, co = 32 * mt + ppg_row_feature(r);
-                if (q > Q || co >= cout) continue;
-                uint16_t *dst = &out[(((size_t)mt * KS + ks) * 64 + lane) * 8];
-                if (q == Q) {   // bias = bf16 head + bf16 remainder
-                    const uint16_t hi = ppg_bf16_bits(bias[co]);
-                    uint32_t hb = (uint32_t)hi << 16;
-                    float hf;
-                    memcpy(&hf, &hb, 4);
-                    dst[0] = hi;
-                    dst[1] = ppg_bf16_bits(bias[co] - hf);
-                    continue;
-                }
-                const int tap = q / cbin, cb = q % cbin;
-                for (int j = 0; j < 8; ++j) {
-                    const int ci = 8 * cb + j;
-                    if (ci < cin) dst[j] = ppg_bf16_bits(w[((size_t)co * cin + ci) * 9 + tap]);
-                }
-            }
-}
-
-// conv1 of the pipeline kernels as fragments of v_mfma_f32_16x16x32_bf16 (ppg_policy_pipe.h: Conv1X), [ky][lane][8]: lane (r = lane &
-// 15 = output channel, kq = lane >> 4) holds for kernel row ky -- kq < 3: the eight input channels 0-7 at tap (ky, kx = kq); kq = 3: the
-// ninth input channel at the taps kx = 0, 1, 2 (elements 0-2; the rest zero).  cin <= 9.
-static void ppg_pack_conv1x(const float *w, int cout, int cin, std::vector<uint16_t> &out) {
-    out.assign((size_t)3 * 64 * 8, 0);
-    for (int ky = 0; ky < 3; ++ky)
-        for (int lane = 0; lane < 64; ++lane) {
-            const int co = lane & 15, kq = lane >> 4;
-            if (co >= cout) continue;
-            uint16_t *dst = &out[((size_t)ky * 64 + lane) * 8];
-            for (int j = 0; j < 8; ++j) {
-                const int ci = kq < 3 ? j : 8, kx = kq < 3 ? kq : j;
-                if (ci < cin && kx < 3) dst[j] = ppg_bf16_bits(w[((size_t)co * cin + ci) * 9 + ky * 3 + kx]);
-            }
-        }
-}
-
-// A Linear layer -> fragments [ks][mt][lane][8] of the 32x32x16 MFMA: lane holds output feature o = 32 mt + row feature(lane & 31) and
-// inputs k = 16 ks + 8 h + j; `value(o, k)` returns the weight (0 for padding)
-template <class Value>
-static void ppg_pack_fc(int K, int mt_n, Value value, std::vector<uint16_t> &out) {
-    const int KS = K / 16;
-    out.assign((size_t)KS * mt_n * 64 * 8, 0);
-    for (int ks = 0; ks < KS; ++ks)
-        for (int mt = 0; mt < mt_n; ++mt)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int r = lane & 31, h = lane >> 5, o = 32 * mt + ppg_row_feature(r);
-                for (int j = 0; j < 8; ++j)
-                    out[(((size_t)ks * mt_n + mt) * 64 + lane) * 8 + j] = ppg_bf16_bits(value(o, 16 * ks + 8 * h + j));
-            }
-}
-
-// the single Linear head of a network without hidden head layers -> fragments of v_mfma_f32_16x16x32_bf16, [action tile][k-step][lane][8]:
-// lane holds action 16 tile + (lane & 15) and the features of area F's elements 32 ks + 8 (lane >> 4) + j; F is [position][flat_c
-// channels] (flat_c = the last convolution's channels padded to blocks of 8); `nhwc`: which feature (channel c, position q) is
-static void ppg_pack_head(const float *hw, int n_actions, int P, int cout_last, bool nhwc, std::vector<uint16_t> &out) {
-    const int flat_c = (cout_last + 7) / 8 * 8, ksteps = (P * flat_c + 31) / 32, head_mt = (n_actions + 15) / 16, flat = P * cout_last;
-    out.assign((size_t)head_mt * ksteps * 64 * 8, 0);
-    for (int mt = 0; mt < head_mt; ++mt)
-        for (int ks = 0; ks < ksteps; ++ks)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int a = 16 * mt + (lane & 15);
-                if (a >= n_actions) continue;
-                for (int j = 0; j < 8; ++j) {
-                    const int e = 32 * ks + 8 * (lane >> 4) + j, q = e / flat_c, c = e % flat_c;
-                    const int ft = (q < P && c < cout_last) ? (nhwc ? q * cout_last + c : c * P + q) : -1;
-                    if (ft >= 0) out[(((size_t)mt * ksteps + ks) * 64 + lane) * 8 + j] = ppg_bf16_bits(hw[(size_t)a * flat + ft]);
-                }
-            }
-}
 
 extern "C" {
 
@@ -1340,67 +1296,6 @@ static int ppg_policy_layout_of(const ppg_policy_spec &sp, bool allow_pipe, ppg_
     return PPG_OK;
 }
 
-// The weights of a spec in the kernels' operand order, one vector per device array: the convolutions, then up to three linear layers (a
-// direct head: wh, whw), conv1 in the pipeline's form, the pipeline's slot table (ppg_policy_layout::slot_tab: not a weight, uploaded with them)
-enum { PPG_FRAG_FC = PPG_POLICY_MAX_CONV, PPG_FRAG_CONV1X = PPG_POLICY_MAX_CONV + 3, PPG_FRAG_SLOTS, PPG_FRAG_N };
-struct ppg_policy_fragments {
-    std::vector<uint16_t> f[PPG_FRAG_N];
-    std::vector<float> bias;   // FC chain: b1, b2, b3 at [0], [256], [512]; direct: head bias at [512]; the pipeline's conv1 bias at [544]
-};
-
-// sp: a spec ppg_policy_check_spec accepts, weight pointers included
-static void ppg_policy_fragments_of(const ppg_policy_spec &sp, ppg_policy_fragments &F) {
-    const int hwc = sp.layout == PPG_POLICY_LAYOUT_HWC, n_actions = sp.n_actions;
-    const int CIN = hwc ? sp.obs_range : sp.obs_channels, P = (hwc ? sp.obs_channels : sp.obs_range) * sp.obs_range;
-    const int cout_last = sp.conv_out[sp.n_conv - 1];
-    const int flat = P * cout_last;   // features behind the flatten
-    const bool nhwc = sp.flatten == PPG_POLICY_FLATTEN_NHWC;
-    std::vector<float> &bias = F.bias;
-    bias.assign(256 + 256 + 32 + 16, 0.0f);
-    int ci = CIN;
-    for (int l = 0; l < sp.n_conv; ++l) {   // input channel blocks: conv1 one or two, then 2, 4, 8; output row tiles: 1, 1, then 2
-        ppg_pack_conv(sp.conv_w[l], sp.conv_b[l], sp.conv_out[l], ci, l == 0 ? (CIN > 8 ? 2 : 1) : l == 1 ? 2 : l == 2 ? 4 : 8, l < 2 ? 1 : 2, F.f[l]);
-        ci = sp.conv_out[l];
-    }
-    if (CIN <= 9) {
-        ppg_pack_conv1x(sp.conv_w[0], sp.conv_out[0], CIN, F.f[PPG_FRAG_CONV1X]);
-        for (int c = 0; c < sp.conv_out[0] && c < 16; ++c) bias[544 + c] = sp.conv_b[0][c];
-    }
-    if (sp.n_fc == 1) {
-        std::vector<uint16_t> &wh = F.f[PPG_FRAG_FC], &whw = F.f[PPG_FRAG_FC + 1];
-        ppg_pack_head(sp.fc_w[0], n_actions, P, cout_last, nhwc, wh);
-        for (int a = 0; a < n_actions; ++a) bias[512 + a] = sp.fc_b[0][a];
-        // whw: wavefront w owns k-steps [w per, (w + 1) per) of action tile 0, its first 18 ride in registers (ppg_policy_direct.h)
-        const int ksteps = (P * ((cout_last + 7) / 8 * 8) + 31) / 32, HFR = 18, per = (ksteps + 3) / 4;
-        whw.assign((size_t)4 * HFR * 64 * 8, 0);
-        for (int w = 0; w < 4; ++w)
-            for (int i = 0; i < HFR && i < per; ++i) {
-                const int ks = w * per + i;
-                if (ks >= ksteps) break;
-                memcpy(&whw[((size_t)w * HFR + i) * 64 * 8], &wh[(size_t)ks * 64 * 8], 64 * 8 * 2);
-            }
-        return;
-    }
-    // FC1: the K order is the scratch slot's [row tile of conv3][position][32 channels]; hidden widths are zero-padded to 256
-    const int h1 = sp.fc_out[0], h2 = sp.n_fc == 3 ? sp.fc_out[1] : 0;
-    const float *w1 = sp.fc_w[0];
-    // feature index of (channel c, position q) behind the flatten, or -1 for a padding channel
-    auto feature = [=](int c, int q) { return c >= cout_last ? -1 : nhwc ? q * cout_last + c : c * P + q; };
-    ppg_pack_fc(64 * P, 8, [&](int o, int k) {
-        const int c = 32 * (k / (32 * P)) + k % 32, q = (k % (32 * P)) / 32, ft = feature(c, q);
-        return (o < h1 && ft >= 0) ? w1[(size_t)o * flat + ft] : 0.0f; }, F.f[PPG_FRAG_FC]);
-    for (int i = 0; i < h1; ++i) bias[i] = sp.fc_b[0][i];
-    if (sp.n_fc == 3) {
-        const float *w2 = sp.fc_w[1];
-        ppg_pack_fc(256, 8, [&](int o, int k) { return (o < h2 && k < h1) ? w2[(size_t)o * h1 + k] : 0.0f; }, F.f[PPG_FRAG_FC + 1]);
-        for (int i = 0; i < h2; ++i) bias[256 + i] = sp.fc_b[1][i];
-    }
-    const float *w3 = sp.fc_w[sp.n_fc - 1];
-    const int hl = sp.n_fc == 3 ? h2 : h1;
-    ppg_pack_fc(256, 1, [&](int o, int k) { return (o < n_actions && k < hl) ? w3[(size_t)o * hl + k] : 0.0f; }, F.f[PPG_FRAG_FC + 2]);
-    for (int i = 0; i < n_actions; ++i) bias[512 + i] = sp.fc_b[sp.n_fc - 1][i];
-}
-
 int ppg_policy_create_spec(int32_t device, const ppg_policy_spec *spec, ppg_policy **out) {
     if (!spec || !out) return ppg_policy_fail(nullptr, PPG_EINVAL, "null argument");
     const ppg_policy_spec &sp = *spec;
@@ -1423,7 +1318,6 @@ int ppg_policy_create_spec(int32_t device, const ppg_policy_spec *spec, ppg_poli
     }
     ppg_policy_fragments F;
     ppg_policy_fragments_of(sp, F);
-    F.f[PPG_FRAG_SLOTS] = L.slot_tab;
     ppg_policy *p = new (std::nothrow) ppg_policy();
     if (!p) return ppg_policy_fail(nullptr, PPG_ENOMEM, "out of host memory");
     memset(p, 0, sizeof *p);   // (every failure below: ppg_policy_destroy frees what exists by then)
@@ -1433,6 +1327,10 @@ int ppg_policy_create_spec(int32_t device, const ppg_policy_spec *spec, ppg_poli
     p->nch16 = CIN > 8;
     p->lds_bytes = L.lds_bytes;
     p->grid = L.wgs_per_cu * prop.multiProcessorCount;
+    p->cus = prop.multiProcessorCount;
+    p->shape = sp;
+    for (int l = 0; l < PPG_POLICY_MAX_CONV; ++l) p->shape.conv_w[l] = p->shape.conv_b[l] = nullptr;
+    for (int l = 0; l < PPG_POLICY_MAX_FC; ++l) p->shape.fc_w[l] = p->shape.fc_b[l] = nullptr;
 #ifdef PPG_EXPERIMENTS
     if (const char *g = getenv("PPG_POLICY_GRID")) p->grid = L.wgs_per_cu == 2 && atoi(g) > 0 ? atoi(g) : p->grid;   // resident workgroups
 #endif
@@ -1445,16 +1343,14 @@ int ppg_policy_create_spec(int32_t device, const ppg_policy_spec *spec, ppg_poli
         p->macs = m;
     }
     const int NF = PPG_FRAG_N;
-    size_t off[NF + 1], total = 0;
-    for (int l = 0; l < NF; ++l) { off[l] = total; total += (F.f[l].size() * 2 + 255) / 256 * 256; }
-    off[NF] = total; total += F.bias.size() * 4;
+    p->image = ppg_policy_image_layout_of(F, L.slot_tab.size());
+    const size_t *off = p->image.off, total = p->image.total;
     if (hipSetDevice(device) != hipSuccess || hipMalloc(&p->dev_weights, total) != hipSuccess) {
         (void)ppg_policy_destroy(p);
         return ppg_policy_fail(nullptr, PPG_EHIP, "hipMalloc of %zu bytes of weights failed", total);
     }
-    std::vector<unsigned char> stage(total, 0);
-    for (int l = 0; l < NF; ++l) if (!F.f[l].empty()) memcpy(stage.data() + off[l], F.f[l].data(), F.f[l].size() * 2);
-    memcpy(stage.data() + off[NF], F.bias.data(), F.bias.size() * 4);
+    std::vector<unsigned char> stage(total);
+    ppg_policy_image_assemble(F, p->image, L.slot_tab.data(), stage.data());
     if (hipMemcpy(p->dev_weights, stage.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
         (void)ppg_policy_destroy(p);
         return ppg_policy_fail(nullptr, PPG_EHIP, "upload of the weights failed");
@@ -1545,6 +1441,95 @@ int ppg_policy_pack(const ppg_policy_spec *spec, int32_t what, uint16_t *out, ui
     return PPG_OK;
 }
 
+int ppg_policy_image(const ppg_policy_spec *spec, int32_t what, void *out, uint64_t capacity, uint64_t *n_bytes) {
+    if (!spec || !n_bytes) return ppg_policy_fail(nullptr, PPG_EINVAL, "null argument");
+    const ppg_policy_spec &sp = *spec;
+    if (what != PPG_POLICY_IMAGE_PACKED && what != PPG_POLICY_IMAGE_REPACKED && what != PPG_POLICY_IMAGE_MAP)
+        return ppg_policy_fail(nullptr, PPG_EINVAL, "ppg_policy_image: unknown image kind %d", what);
+    int rc = ppg_policy_check_spec(sp, what != PPG_POLICY_IMAGE_MAP);
+    if (rc != PPG_OK) return rc;
+    ppg_policy_layout L;
+    if ((rc = ppg_policy_layout_of(sp, ppg_pipe_enabled(), L)) != PPG_OK) return rc;
+    std::vector<int32_t> map;
+    std::vector<unsigned char> image;
+    ppg_policy_image_layout I;
+    if (what != PPG_POLICY_IMAGE_PACKED) ppg_policy_map_of(sp, L.slot_tab.size(), map, I);
+    if (what != PPG_POLICY_IMAGE_MAP) {
+        ppg_policy_fragments F;
+        ppg_policy_fragments_of(sp, F);
+        const ppg_policy_image_layout P = ppg_policy_image_layout_of(F, L.slot_tab.size());
+        image.resize(P.total);
+        ppg_policy_image_assemble(F, P, L.slot_tab.data(), image.data());
+        if (what == PPG_POLICY_IMAGE_REPACKED) {   // of the packed image only the slot table's section survives
+            if (I.total != P.total || I.off[PPG_FRAG_SLOTS] != P.off[PPG_FRAG_SLOTS] || I.off[PPG_FRAG_N] != P.off[PPG_FRAG_N])
+                return ppg_policy_fail(nullptr, PPG_EINVAL, "ppg_policy_image: the map and the fragments disagree about the image's layout");
+            memset(image.data(), 0xA5, I.off[PPG_FRAG_SLOTS]);
+            memset(image.data() + I.off[PPG_FRAG_N], 0xA5, I.total - I.off[PPG_FRAG_N]);
+            const ppg_policy_sources S = ppg_policy_sources_of(sp);
+            ppg_policy_repack_cpu(map.data(), S.t, image.data());
+        }
+    }
+    const void *from = what == PPG_POLICY_IMAGE_MAP ? (const void *)map.data() : (const void *)image.data();
+    *n_bytes = what == PPG_POLICY_IMAGE_MAP ? (uint64_t)map.size() * 4 : (uint64_t)image.size();
+    if (out && capacity >= *n_bytes) memcpy(out, from, (size_t)*n_bytes);
+    return PPG_OK;
+}
+
+// the first field in which spec `b` differs from the shape `a` (NULL: none); `va` / `vb` get the two values
+static const char *ppg_policy_shape_diff(const ppg_policy_spec &a, const ppg_policy_spec &b, int *va, int *vb) {
+    static char name[32];
+#define PPG_SHAPE_FIELD(f) if (a.f != b.f) { *va = a.f; *vb = b.f; return #f; }
+    PPG_SHAPE_FIELD(obs_channels) PPG_SHAPE_FIELD(obs_range) PPG_SHAPE_FIELD(n_actions) PPG_SHAPE_FIELD(layout) PPG_SHAPE_FIELD(flatten)
+    PPG_SHAPE_FIELD(n_conv) PPG_SHAPE_FIELD(n_fc)
+#undef PPG_SHAPE_FIELD
+    for (int l = 0; l < a.n_conv; ++l)
+        if (a.conv_out[l] != b.conv_out[l]) { *va = a.conv_out[l]; *vb = b.conv_out[l]; snprintf(name, sizeof name, "conv_out[%d]", l); return name; }
+    for (int l = 0; l < a.n_fc; ++l)
+        if (a.fc_out[l] != b.fc_out[l]) { *va = a.fc_out[l]; *vb = b.fc_out[l]; snprintf(name, sizeof name, "fc_out[%d]", l); return name; }
+    return nullptr;
+}
+
+int ppg_policy_update(ppg_policy *p, const ppg_policy_spec *spec, void *stream) {
+    if (!p) return ppg_policy_fail(nullptr, PPG_EINVAL, "ppg_policy_update: the policy is NULL");
+    if (!spec) return ppg_policy_fail(p, PPG_EINVAL, "ppg_policy_update: spec is NULL");
+    const ppg_policy_spec &sp = *spec;
+    int was = 0, is = 0;
+    if (const char *field = ppg_policy_shape_diff(p->shape, sp, &was, &is))
+        return ppg_policy_fail(p, PPG_EINVAL, "ppg_policy_update: %s is %d, the policy was created with %d", field, is, was);
+    for (int l = 0; l < sp.n_conv; ++l)
+        if (!sp.conv_w[l] || !sp.conv_b[l]) return ppg_policy_fail(p, PPG_EINVAL, "ppg_policy_update: a weight pointer of convolution %d is NULL", l + 1);
+    for (int l = 0; l < sp.n_fc; ++l)
+        if (!sp.fc_w[l] || !sp.fc_b[l]) return ppg_policy_fail(p, PPG_EINVAL, "ppg_policy_update: a weight pointer of linear layer %d is NULL", l + 1);
+    const size_t W = p->image.off[PPG_FRAG_SLOTS] / 2, n_bias = p->image.n_bias;
+    if (!p->map_dev) {   // the first update of this policy: build the map and upload it (blocks; not inside a stream capture)
+        std::vector<int32_t> map;
+        ppg_policy_image_layout I;
+        ppg_policy_map_of(p->shape, p->image.words[PPG_FRAG_SLOTS], map, I);
+        if (I.total != p->image.total || I.off[PPG_FRAG_SLOTS] != p->image.off[PPG_FRAG_SLOTS] || I.off[PPG_FRAG_N] != p->image.off[PPG_FRAG_N])
+            return ppg_policy_fail(p, PPG_EINVAL, "ppg_policy_update: the map and the policy disagree about the image's layout");
+        const size_t bytes = (W + n_bias) * sizeof(int32_t);
+        int32_t *dev = nullptr;
+        PPG_POL_TRY(p, hipSetDevice(p->device));
+        PPG_POL_TRY(p, hipMalloc((void **)&dev, bytes));
+        if (hipMemcpy(dev, map.data() + PPG_MAP_HEADER, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(dev);
+            return ppg_policy_fail(p, PPG_EHIP, "ppg_policy_update: upload of the repack map failed");
+        }
+        p->map_dev = dev;
+    }
+    ppgpol::RepackParams K;
+    const ppg_policy_sources S = ppg_policy_sources_of(sp);
+    for (int t = 0; t < PPG_SRC_N; ++t) K.src[t] = S.t[t];
+    K.map = p->map_dev;
+    K.image = (ppgpol::u32x4_t *)p->dev_weights;
+    K.bias = (float *)((unsigned char *)p->dev_weights + p->image.off[PPG_FRAG_N]);
+    K.n_units = (uint32_t)(W / 8); K.n_bias = (uint32_t)n_bias;
+    const uint32_t need = (K.n_units + K.n_bias + 255u) / 256u, most = 8u * (uint32_t)p->cus;   // (eight workgroups of 256 fill a CU's wavefront slots)
+    hipLaunchKernelGGL(ppgpol::ppg_policy_repack, dim3(need < most ? need : most), dim3(256), 0, (hipStream_t)stream, K);
+    PPG_POL_TRY(p, hipGetLastError());
+    return PPG_OK;
+}
+
 int ppg_policy_describe(const ppg_policy_spec *spec, int32_t *out, int32_t n) {
     if (!spec || !out || n < 1) return PPG_EINVAL;
     ppg_policy_layout L;
@@ -1566,6 +1551,7 @@ int ppg_policy_destroy(ppg_policy *p) {
     if (p->plan) (void)hipFree(p->plan);
     if (p->pre_g) (void)hipFree(p->pre_g);
     if (p->lgs) (void)hipFree(p->lgs);
+    if (p->map_dev) (void)hipFree(p->map_dev);
     if (p->side) (void)hipStreamDestroy(p->side);
     if (p->fork) (void)hipEventDestroy(p->fork);
     if (p->join) (void)hipEventDestroy(p->join);

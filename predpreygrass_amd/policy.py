@@ -198,8 +198,8 @@ def load_rllib_state_dict(state_dict, obs_range: int = None, obs_channels: int =
 class FusedPolicy:
     """The two species' networks on the matrix cores, next to the envs.
 
-    pred_net / prey_net: `PolicyNet`s (any device; the float32 weights are copied once).  Either may be None: that species
-    keeps whatever the action tensor holds."""
+    pred_net / prey_net: `PolicyNet`s (any device; the float32 weights are copied once, `update()` replaces them from the device).
+    Either may be None: that species keeps whatever the action tensor holds."""
 
     def __init__(self, pred_net: PolicyNet = None, prey_net: PolicyNet = None, device="cuda:0"):
         self._lib = _abi.load_hip_library()
@@ -212,16 +212,19 @@ class FusedPolicy:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self._handles = [self._create(pred_net), self._create(prey_net)]
         self.nets = (pred_net, prey_net)
+        self._archs = [None if net is None else self._arch(net) for net in self.nets]
+        self._staged = [[], []]   # update(): device copies of parameters that could not be read in place
+        self._closed = False
 
-    def _create(self, net):
-        if net is None:
-            return None
-        keep = []   # the host arrays must live until ppg_policy_create_spec returns
+    @staticmethod
+    def _arch(net):
+        """What an update must find unchanged: how the observation is read and flattened, and the shape of every parameter."""
+        return (net.obs_channels, net.obs_range, net.n_actions, net.layout, net.flatten,
+                tuple(tuple(m.weight.shape) + tuple(m.bias.shape) for m in net.conv + net.fc))
 
-        def host(t):
-            a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
-            keep.append(a)
-            return a.ctypes.data
+    @staticmethod
+    def _spec(net, pointer):
+        """`ppg_policy_spec` of a net; pointer(parameter) is the address the library reads it from."""
         convs, fcs = net.conv, net.fc
         if len(convs) > _abi.POLICY_MAX_CONV or len(fcs) > _abi.POLICY_MAX_FC:
             raise ValueError(f"{len(convs)} convolutions / {len(fcs)} linear layers: the kernels take up to "
@@ -232,9 +235,21 @@ class FusedPolicy:
         sp.flatten = _abi.POLICY_FLATTEN_NHWC if net.flatten == "nhwc" else _abi.POLICY_FLATTEN_NCHW
         sp.n_conv, sp.n_fc = len(convs), len(fcs)
         for l, m in enumerate(convs):
-            sp.conv_out[l], sp.conv_w[l], sp.conv_b[l] = m.out_channels, host(m.weight), host(m.bias)
+            sp.conv_out[l], sp.conv_w[l], sp.conv_b[l] = m.out_channels, pointer(m.weight), pointer(m.bias)
         for l, m in enumerate(fcs):
-            sp.fc_out[l], sp.fc_w[l], sp.fc_b[l] = m.out_features, host(m.weight), host(m.bias)
+            sp.fc_out[l], sp.fc_w[l], sp.fc_b[l] = m.out_features, pointer(m.weight), pointer(m.bias)
+        return sp
+
+    def _create(self, net):
+        if net is None:
+            return None
+        keep = []   # the host arrays must live until ppg_policy_create_spec returns
+
+        def host(t):
+            a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
+            keep.append(a)
+            return a.ctypes.data
+        sp = self._spec(net, host)
         h = C.c_void_p()
         rc = self._lib.ppg_policy_create_spec(self.device.index, C.byref(sp), C.byref(h))
         if rc != 0:
@@ -243,6 +258,53 @@ class FusedPolicy:
                 raise ValueError(msg)
             raise RuntimeError(f"ppg_policy_create_spec failed ({rc}): {msg}")
         return h
+
+    def update(self, pred_net: PolicyNet = None, prey_net: PolicyNet = None, stream=None):
+        """New weights for the networks that act, read on the device (`ppg_policy_update`): the learner-to-actor hand-over after
+        `optimizer.step()`.  None leaves that species as it is.  A parameter that is float32, contiguous and on the policy's device
+        is read IN PLACE -- no copy, no host wait; the kernel reads it when it runs, so the call is ordered on `stream` (default:
+        the current stream) like an `act()`, behind whatever wrote the parameters.  Any other parameter (a CPU net, bf16 / float64,
+        non-contiguous) is first staged with `.to(device, torch.float32)`; the staged tensors stay referenced until the species'
+        next update or `close()`.  The weights land in the buffers the kernels already read: captured loops (`GraphedPolicyStep`,
+        `trajectory.GraphedCollector`) act with them at their next replay, and the call itself can be captured -- after one eager
+        update of the policy, which allocates the repack map.  ValueError, before anything is launched: another architecture than
+        the species was created with, a net for a species created as None, a closed policy.  `self.nets` follows; returns self."""
+        if self._closed:
+            raise ValueError("the policy is closed")
+        given = (pred_net, prey_net)
+        for t, net in enumerate(given):
+            if net is None:
+                continue
+            name = ("pred_net", "prey_net")[t]
+            if self._handles[t] is None:
+                raise ValueError(f"{name} was given but the policy was created without a network for that species")
+            arch = self._arch(net)
+            if arch != self._archs[t]:
+                raise ValueError(f"{name} has another architecture than the policy was created with: "
+                                 f"(obs_channels, obs_range, n_actions, layout, flatten, parameter shapes) = {arch}, created with {self._archs[t]}")
+        s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if stream is None else \
+            C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
+        for t, net in enumerate(given):
+            if net is None:
+                continue
+            staged = []
+
+            def device(p):
+                x = p.detach()
+                if x.dtype == torch.float32 and x.device == self.device and x.is_contiguous():
+                    return x.data_ptr()
+                staged.append(_alloc_on(self.device, stream, lambda: x.to(self.device, torch.float32).contiguous()))
+                return staged[-1].data_ptr()
+            sp = self._spec(net, device)
+            self._staged[t] = staged
+            rc = self._lib.ppg_policy_update(self._handles[t], C.byref(sp), s)
+            if rc != 0:
+                msg = self._lib.ppg_policy_last_error(self._handles[t]).decode()
+                if rc == -1:
+                    raise ValueError(msg)
+                raise RuntimeError(f"ppg_policy_update failed ({rc}): {msg}")
+            self.nets = tuple(net if k == t else old for k, old in enumerate(self.nets))
+        return self
 
     def macs_per_observation(self, species: int) -> int:
         h = self._handles[species]
@@ -304,6 +366,8 @@ class FusedPolicy:
             if h:
                 self._lib.ppg_policy_destroy(h)
         self._handles = [None, None]
+        self._staged = [[], []]
+        self._closed = True
 
     def __del__(self):
         try:
@@ -320,7 +384,8 @@ class GraphedPolicyStep:
         loop = GraphedPolicyStep(fused, env, seed=0); loop.replay(1000)
 
     The key of step t is seed + t, kept in a device word the captured increment advances; results equal `fused.act(env, sample=True,
-    seed=seed + t); env.step(env.actions, auto_reset=True)` step by step (tests/test_policy.py)."""
+    seed=seed + t); env.step(env.actions, auto_reset=True)` step by step (tests/test_policy.py).
+    After `fused.update(...)` the next replay acts with the new weights: they land where the captured kernels read them."""
 
     def __init__(self, fused: "FusedPolicy", env, seed: int = 0, sample: bool = True, auto_reset: bool = True):
         self.fused, self.env = fused, env

@@ -749,7 +749,8 @@ class GraphedCollector:
         logp, entropy, dist = traj.behaviour(PREY)
 
     The warm pass acts on an output no record() has stored, so its record_policy() writes nothing; replay i stores the policy of
-    step i - 1, and the samples of the last recorded step keep NaN."""
+    step i - 1, and the samples of the last recorded step keep NaN.
+    After `fused.update(...)` the next replay acts with the new weights: they land where the captured kernels read them."""
 
     def __init__(self, env, traj, act=None, auto_reset=True, logits=None):
         if not getattr(traj, "step_on_device", False):
