@@ -923,6 +923,48 @@ int ppg_policy_update(ppg_policy *p, const ppg_policy_spec *spec, void *stream);
 #define PPG_POLICY_IMAGE_MAP 2
 int ppg_policy_image(const ppg_policy_spec *spec, int32_t what, void *out, uint64_t capacity, uint64_t *n_bytes);
 
+/* The network of a policy over a DENSE tensor of observation rows -- the sample store ppg_record_obs fills, or any [rows][C][R][R]
+ * tensor -- instead of the rows in use of a handle: a critic's values for every stored sample (a critic is a network with
+ * n_actions = 1: its one "logit" is the value), or the actor's logits under its current weights, on the matrix cores.  The forward
+ * kernels are ppg_policy_act's, launched once for one species; what differs is where their plan comes from: a kernel of its own,
+ * ppg_policy_plan_rows in csrc/ppg_policy.h, writes it in closed form from the row count (csrc/ppg_policy_plan.h).
+ * Rows [0, min(max(count, 0), capacity)) of `out` receive the float32 outputs, BIT FOR BIT what ppg_policy_act writes into its logits
+ * tensor for the same observation row and weights (same kernels, same arithmetic; a row's result does not depend on its position or
+ * on the count).  Rows at and behind the count keep what they held.  Outputs are those of PPG_POLICY_ARGMAX: no Philox key is
+ * involved, and the action byte the kernels store per sample goes to a scratch the policy owns.
+ * The count is `count`, or -- count_dev != NULL -- one int64 in device memory that the plan kernel reads WHEN IT RUNS (a word of the
+ * store's cursor): nothing is read back and the host never waits.
+ * The policy keeps a plan buffer and the action scratch for this call, apart from ppg_policy_act's plan (an evaluate between two acts
+ * moves nothing a graph captured around ppg_policy_act reads); they are allocated at the first call and whenever `capacity` exceeds
+ * every earlier call's, and freed by ppg_policy_destroy.  Such a call must not stand inside a stream capture; every LATER call at a
+ * capacity up to that one only launches (two kernels) and can be captured.
+ * ORDER: the forward kernels' scratch belongs to the policy, so an evaluate is ordered like an act: on one stream with the policy's
+ * other calls (act, update, evaluate), and behind whatever wrote the rows and the count.
+ * PPG_EINVAL with a message, before anything is launched: p or rows NULL, obs or out NULL with capacity > 0, an obs_dtype other than
+ * 0 / 1 / 2 (the cell layout is not taken), capacity < 0 or above 2^30.  capacity == 0, or count <= 0 with count_dev NULL: PPG_OK
+ * without a launch.  The checks of ppg_policy_act that speak about a handle (nine actions in the base env, 64 predator rows) do not
+ * apply: there is no handle. */
+typedef struct ppg_policy_rows {
+    const void *obs;          /* device, dense [capacity][C][R][R], element type obs_dtype */
+    int32_t obs_dtype;        /* ppg_config.obs_dtype's codes: 0 float64, 1 float32, 2 bfloat16 (not the cell layout) */
+    int64_t capacity;         /* rows the tensors have */
+    int64_t count;            /* rows to evaluate, used when count_dev is NULL */
+    const int64_t *count_dev; /* or: one int64 on the device, read by the plan kernel when it runs */
+    float *out;               /* device, float32 [capacity][n_actions] */
+} ppg_policy_rows;
+int ppg_policy_evaluate(ppg_policy *p, const ppg_policy_rows *rows, void *stream);
+
+/* Diagnostic, device-free like ppg_policy_image: the words the plan kernel of ppg_policy_evaluate writes for `count` of `capacity` rows
+ * and a forward grid of `slots` workgroups, made by the same inline functions on the CPU -- so that the plan can be checked where
+ * there is no GPU.  The words: [0] rows to evaluate, [1], [2] as the network's kernels read them (FC chain: full tiles of 128, samples
+ * per tile of the last round; direct head / pipeline: samples of a workgroup's share, tiles per workgroup), then the exclusive prefix
+ * sums of the ceil(capacity / PPG_POLICY_ROWS_CHUNK) pseudo-envs the rows are read as, then the pseudo-env of every tile's first
+ * sample.  *n_words = their number; out == NULL or capacity_words too small: only the size is reported (PPG_OK).  PPG_EINVAL: a spec
+ * ppg_policy_create_spec would reject on its shape, slots < 1, capacity outside [0, 2^30].  The weight pointers are not read. */
+#define PPG_POLICY_ROWS_CHUNK 128   /* rows per pseudo-env; the results of ppg_policy_evaluate do not depend on it */
+int ppg_policy_rows_plan(const ppg_policy_spec *spec, int32_t slots, int64_t capacity, int64_t count, uint32_t *out,
+                         uint64_t capacity_words, uint64_t *n_words);
+
 /* A device buffer for the caller-owned observation tensors whose physical pages are picked at random from a stretch of device
  * memory `spread` times its size (HIP virtual memory management: spread x as many 2 MB chunks are created, a random subset is
  * mapped in random order, the rest is given back at once).  Optional -- any device pointer works as obs_pred / obs_prey -- but where

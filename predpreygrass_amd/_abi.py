@@ -191,10 +191,18 @@ POLICY_LAYOUT_CHW, POLICY_LAYOUT_HWC = 0, 1
 POLICY_FLATTEN_NCHW, POLICY_FLATTEN_NHWC = 0, 1
 POLICY_SYMBOLS = ["ppg_policy_create", "ppg_policy_create_layout", "ppg_policy_create_spec", "ppg_policy_destroy", "ppg_policy_act",
                   "ppg_policy_macs_per_observation", "ppg_policy_last_error", "ppg_policy_describe", "ppg_policy_pack",
-                  "ppg_policy_update", "ppg_policy_image"]
+                  "ppg_policy_update", "ppg_policy_image", "ppg_policy_evaluate", "ppg_policy_rows_plan"]
 POLICY_PACK_CONV1X, POLICY_PACK_HEAD, POLICY_PACK_SLOTS = 100, 200, 300
 POLICY_IMAGE_PACKED, POLICY_IMAGE_REPACKED, POLICY_IMAGE_MAP = 0, 1, 2
 POLICY_MAP_HEADER = 32   # int32 words in front of the entries of POLICY_IMAGE_MAP (include/ppg.h)
+POLICY_ROWS_CHUNK = 128  # rows per pseudo-env of ppg_policy_rows_plan's words (include/ppg.h: PPG_POLICY_ROWS_CHUNK)
+POLICY_PLAN_HEADER = 3   # words in front of the prefix sums of a plan
+
+
+class PpgPolicyRows(C.Structure):
+    """include/ppg.h: struct ppg_policy_rows (a dense tensor of observation rows for ppg_policy_evaluate)."""
+    _fields_ = [("obs", C.c_void_p), ("obs_dtype", C.c_int32), ("capacity", C.c_int64), ("count", C.c_int64),
+                ("count_dev", C.c_void_p), ("out", C.c_void_p)]
 
 
 SPREAD_SYMBOLS = ["ppg_alloc_spread", "ppg_free_spread", "ppg_spread_stats", "ppg_spread_last_error"]   # HIP library only, like the policy symbols
@@ -313,6 +321,11 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.ppg_policy_update.argtypes = [C.c_void_p, C.POINTER(PpgPolicySpec), C.c_void_p]
         lib.ppg_policy_image.restype = C.c_int
         lib.ppg_policy_image.argtypes = [C.POINTER(PpgPolicySpec), C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.ppg_policy_evaluate.restype = C.c_int
+        lib.ppg_policy_evaluate.argtypes = [C.c_void_p, C.POINTER(PpgPolicyRows), C.c_void_p]
+        lib.ppg_policy_rows_plan.restype = C.c_int
+        lib.ppg_policy_rows_plan.argtypes = [C.POINTER(PpgPolicySpec), C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_uint64,
+                                             C.POINTER(C.c_uint64)]
         lib.ppg_policy_macs_per_observation.restype = C.c_uint64
         lib.ppg_policy_macs_per_observation.argtypes = [C.c_void_p]
         lib.ppg_policy_last_error.restype = C.c_char_p

@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "ppg_policy_pack.h"
+#include "ppg_policy_plan.h"
 
 namespace ppgpol {
 
@@ -48,10 +49,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 #define GLOBAL_AS __attribute__((address_space(1)))   // pointers known to be global memory: global_* instead of flat_* instructions
 
-constexpr int TILE = 128;         // samples per workgroup tile
+constexpr int TILE = (int)PPG_PLAN_TILE;   // samples per workgroup tile (128)
 constexpr int HSTRIDE = 264;      // H[sample][256 + 8] bf16: rows 528 B apart -> conflict-free 16-byte fragment reads
 constexpr int MAX_HANDLES = PPG_PACK_MAX_HANDLES;
-constexpr int PLAN_HDR = 3;       // words in front of the prefix sums of PolParams::plan
+constexpr int PLAN_HDR = PPG_PLAN_HDR;     // words in front of the prefix sums of PolParams::plan (3)
 
 struct PolParams {
     // geometry
@@ -209,17 +210,18 @@ __device__ __forceinline__ void plan_body(const PlanParams &K) {
         // RANGE MODE: workgroup w owns samples [w S, (w + 1) S), S = the per-workgroup share rounded up to whole sub-groups, as tiles of
         // range_tile samples -- every workgroup the same number of FULL sub-groups (whole rounds of 128-sample tiles + a short last round
         // leave most of the chip idle in the last round and cut a two-sample sub-group off every tile: 7 % at the benchmark's 132 k prey)
-        const uint32_t st = (uint32_t)K.range_st, slots = (uint32_t)K.slots, tsz = (uint32_t)K.range_tile;
-        const uint32_t S = st * ((all + slots * st - 1u) / (slots * st));
-        const uint32_t tpw = S ? (S + tsz - 1u) / tsz : 1u;
+        // (the arithmetic: ppg_policy_plan.h, shared with ppg_policy_plan_rows)
+        const uint32_t slots = (uint32_t)K.slots, tsz = (uint32_t)K.range_tile;
+        const ppg_plan_range rg = ppg_plan_range_of(all, slots, (uint32_t)K.range_st, tsz);
+        const uint32_t S = rg.share, tpw = rg.tpw;
         if (t == 0) { K.plan[0] = all; K.plan[1] = S; K.plan[2] = tpw; }
         __threadfence_block();
         __syncthreads();
         const int n_slots = (int)(slots * tpw);
         for (int tile = t; tile < n_slots; tile += 1024) {
-            uint32_t n = ((uint32_t)tile / tpw) * S + ((uint32_t)tile % tpw) * tsz;
+            uint32_t n = ppg_plan_range_slot((uint32_t)tile, S, tpw, tsz);
             if (all == 0u) { K.tile_env[tile] = 0u; continue; }
-            if (n > all - 1u) n = all - 1u;    // (an empty tile slot: behind every sample of the tiles in front of it -- keeps the list monotone)
+            n = ppg_plan_range_clamp(n, all);    // (an empty tile slot: behind every sample of the tiles in front of it -- keeps the list monotone)
             int ua = 0, ub = 1023;
             while (ua < ub) {
                 const int mid = (ua + ub + 1) >> 1;
@@ -239,21 +241,17 @@ __device__ __forceinline__ void plan_body(const PlanParams &K) {
     // spread over the slots in tiles of 32 / 64 / 96 / 128.  A last round of a few full tiles would take as long as any other
     // round while most of the chip idles: at the benchmark's 134 k prey rows, 1047 tiles of 128 on 512 slots are 2.04 rounds and
     // cost three; 1024 + 92 tiles of 32 cost two and a short one.
-    const uint32_t per_round = (uint32_t)TILE * (uint32_t)K.slots;
-    uint32_t n_full = (all / per_round) * (uint32_t)K.slots;
-    const uint32_t rest = all - n_full * (uint32_t)TILE;
-    uint32_t ts = 32u * ((rest + 32u * (uint32_t)K.slots - 1u) / (32u * (uint32_t)K.slots));   // 32 * ceil(rest / (32 * slots))
-    if (ts < 32u) ts = 32u;
-    if (K.force_ts) { ts = (uint32_t)K.force_ts; n_full = 0; }
+    // (the arithmetic: ppg_policy_plan.h, shared with ppg_policy_plan_rows)
+    const ppg_plan_tiles tl = ppg_plan_tiles_of(all, (uint32_t)K.slots, (uint32_t)K.force_ts);
+    const uint32_t n_full = tl.n_full, ts = tl.ts;
     if (t == 0) { K.plan[0] = all; K.plan[1] = n_full; K.plan[2] = ts; }
     __threadfence_block();
     __syncthreads();   // (the prefix sums are re-read below by other threads of this workgroup: same CU, written through L1)
-    const uint32_t tail = all - n_full * (uint32_t)TILE;
-    const int n_tiles = (int)(n_full + (tail + ts - 1) / ts);
+    const int n_tiles = (int)ppg_plan_tile_count(all, n_full, ts);
     // exclusive prefix of thread u's run = part[u] - (its own sum) = part[u - 1]: the bisection first finds the RUN in LDS (ten steps, no
     // memory round trip), then the env inside the run (`per` <= a handful of prefix sums from memory)
     for (int tile = t; tile < n_tiles; tile += 1024) {
-        const uint32_t n = (uint32_t)tile < n_full ? (uint32_t)tile * (uint32_t)TILE : n_full * (uint32_t)TILE + ((uint32_t)tile - n_full) * ts;
+        const uint32_t n = ppg_plan_tile_first((uint32_t)tile, n_full, ts);
         int ua = 0, ub = 1023;
         while (ua < ub) {   // the last run whose first env's prefix sum (= the inclusive sum of the runs before it) is <= n
             const int mid = (ua + ub + 1) >> 1;
@@ -272,6 +270,22 @@ extern "C" __global__ void __launch_bounds__(1024) ppg_policy_plan_small(const P
 // both species' plans in one launch (workgroup 0: A, workgroup 1: B): one launch and one dependent-load chain less per step
 extern "C" __global__ void __launch_bounds__(1024) ppg_policy_plan2(const PlanParams A, const PlanParams B) {
     if (blockIdx.x == 0) plan_body<true>(A); else plan_body<true>(B);
+}
+
+// The plan of a DENSE ROW TENSOR (ppg_policy_evaluate; ppg_policy_plan.h, part 2): the words plan_body would write for pseudo-envs of
+// PPG_POLICY_ROWS_CHUNK rows of which the first `count` rows are in use, in closed form -- no scan, no bisection, no item depends on
+// another, so it is a plain grid-stride loop.  The count is an argument, or a device word read HERE (nothing is read back).
+struct RowsPlanParams {
+    int64_t capacity, count;
+    const int64_t *count_dev;
+    uint32_t slots, range_tile, range_st;
+    uint32_t *plan;                    // [PLAN_HDR + envs] header + prefix sums, then the first env of every tile
+};
+extern "C" __global__ void __launch_bounds__(256) ppg_policy_plan_rows(const RowsPlanParams K) {
+    const int64_t count = K.count_dev ? *K.count_dev : K.count;
+    const ppg_rows_shape s = ppg_rows_shape_of(K.capacity, count, K.slots, K.range_tile, K.range_st);
+    uint32_t *tile_env = K.plan + PLAN_HDR + s.n_envs;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < s.items; i += gridDim.x * 256u) ppg_rows_item(i, s, K.plan, tile_env);
 }
 
 __device__ __forceinline__ bf16x8 zero8() {
@@ -1036,6 +1050,11 @@ struct ppg_policy {
     uint32_t *plan;        // [PLAN_HDR + plan_envs] header + prefix sums, then the first env of every tile
     int32_t plan_envs;
     size_t plan_words;     // words the buffer was allocated with (it depends on the species' row capacity too)
+    // ppg_policy_evaluate's own plan (never ppg_policy_act's: an evaluate between two acts must move nothing a captured act reads) and
+    // the scratch its forward launch stores the action bytes into; sized for the largest capacity seen
+    uint32_t *rows_plan;
+    int8_t *rows_actions;
+    int64_t rows_capacity;
     uint32_t *pre_g;       // the fused launch's prefix sums in memory (PolParams2::pre_g), [2][FUSED_MAX_ENVS]; owned by the prey's policy
     int32_t grid;
     int32_t lds_bytes;
@@ -1549,6 +1568,8 @@ int ppg_policy_destroy(ppg_policy *p) {
     if (p->dev_weights) (void)hipFree(p->dev_weights);
     if (p->xg) { if (p->xg_is_spread) (void)ppg_free_spread(p->xg); else (void)hipFree(p->xg); }
     if (p->plan) (void)hipFree(p->plan);
+    if (p->rows_plan) (void)hipFree(p->rows_plan);
+    if (p->rows_actions) (void)hipFree(p->rows_actions);
     if (p->pre_g) (void)hipFree(p->pre_g);
     if (p->lgs) (void)hipFree(p->lgs);
     if (p->map_dev) (void)hipFree(p->map_dev);
@@ -1760,6 +1781,8 @@ static int ppg_policy_fill(ppg_policy *p, int species, ppg_handle *const *handle
     return PPG_OK;
 }
 
+static int ppg_policy_forward(ppg_policy *p, const ppgpol::PolParams &K, void *stream);
+
 // also_plan_for: the OTHER species' policy whose plan this call's plan launch computes as well (ppg_policy_plan2); skip_plan: this
 // species' plan was computed by the other call
 static int ppg_policy_run(ppg_policy *p, int species, ppg_handle *const *handles, int32_t n, int8_t *const *actions, uint32_t flags,
@@ -1795,6 +1818,13 @@ static int ppg_policy_run(ppg_policy *p, int species, ppg_handle *const *handles
     } else if (!skip_plan) {
         hipLaunchKernelGGL(p->direct ? ppgpol::ppg_policy_plan : ppgpol::ppg_policy_plan_small, dim3(1), dim3(1024), 0, (hipStream_t)stream, L);
     }
+    if ((rc = ppg_policy_forward(p, K, stream)) != PPG_OK) return rc;   // (its hipGetLastError() speaks for the plan launch too)
+    return ppg_policy_diag_after(p, species, total, K);
+}
+
+// the single-species forward launch of a filled parameter block: the kernel family, input-channel variant and row dtype pick the kernel
+static int ppg_policy_forward(ppg_policy *p, const ppgpol::PolParams &K, void *stream) {
+    int rc;
     typedef void (*fwd_fn)(const ppgpol::PolParams);
     const fwd_fn fwd[3][3] = {{ppgpol::ppg_policy_forward_f64, ppgpol::ppg_policy_forward_f32, ppgpol::ppg_policy_forward_bf16},
                               {ppgpol::ppg_policy_forward_hwc8_f64, ppgpol::ppg_policy_forward_hwc8_f32, ppgpol::ppg_policy_forward_hwc8_bf16},
@@ -1816,7 +1846,7 @@ static int ppg_policy_run(ppg_policy *p, int species, ppg_handle *const *handles
         hipLaunchKernelGGL(fwd[variant][dt], dim3((unsigned)p->grid), dim3(256), (size_t)p->lds_bytes, (hipStream_t)stream, K);
     }
     PPG_POL_TRY(p, hipGetLastError());
-    return ppg_policy_diag_after(p, species, total, K);
+    return PPG_OK;
 }
 
 // diagnostic switch: environment variable PPG_POLICY_FUSED=0 sends a call with both species' pipeline policies through the two
@@ -1913,6 +1943,79 @@ int ppg_policy_act(ppg_policy *pred, ppg_policy *prey, ppg_handle *const *handle
         PPG_POL_TRY(pred, hipEventRecord(pred->join, pred->side));
         PPG_POL_TRY(pred, hipStreamWaitEvent((hipStream_t)stream, pred->join, 0));
     }
+    return PPG_OK;
+}
+
+// the plan mode of a policy's forward kernels as the plan kernels take it: range_tile > 0 = range mode with sub-groups of range_st
+static void ppg_policy_plan_mode(int direct, const ppgpol::PolParams &K, uint32_t &range_tile, uint32_t &range_st) {
+    range_tile = direct ? (uint32_t)K.range_tile : 0u;
+    range_st = (uint32_t)K.ST;
+}
+
+// The network over a dense row tensor (include/ppg.h).  The rows are one "handle" of ceil(capacity / CH) pseudo-envs with S = cap = CH
+// and slot0 = 0: the forward kernels' addresses are then linear in the sample number (ppg_policy_plan.h).  The kernels, their constant
+// parameters (p->base) and their selection are ppg_policy_run's; the plan comes from ppg_policy_plan_rows into a buffer of its own.
+int ppg_policy_evaluate(ppg_policy *p, const ppg_policy_rows *rows, void *stream) {
+    if (!p) return ppg_policy_fail(nullptr, PPG_EINVAL, "ppg_policy_evaluate: the policy is NULL");
+    if (!rows) return ppg_policy_fail(p, PPG_EINVAL, "ppg_policy_evaluate: rows is NULL");
+    const ppg_policy_rows &r = *rows;
+    if (r.capacity < 0 || r.capacity > PPG_ROWS_MAX)
+        return ppg_policy_fail(p, PPG_EINVAL, "ppg_policy_evaluate: capacity %lld is outside [0, %lld]", (long long)r.capacity, (long long)PPG_ROWS_MAX);
+    if (r.obs_dtype == 3) return ppg_policy_fail(p, PPG_EINVAL, "ppg_policy_evaluate: rows in the cell layout (obs_dtype 3) are not taken");
+    if (r.obs_dtype < 0 || r.obs_dtype > 2)
+        return ppg_policy_fail(p, PPG_EINVAL, "ppg_policy_evaluate: unknown obs_dtype %d (0 float64, 1 float32, 2 bfloat16)", r.obs_dtype);
+    if (r.capacity > 0 && (!r.obs || !r.out)) return ppg_policy_fail(p, PPG_EINVAL, "ppg_policy_evaluate: %s is NULL", r.obs ? "out" : "obs");
+    if (r.capacity == 0 || (!r.count_dev && r.count <= 0)) return PPG_OK;
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != p->device) PPG_POL_TRY(p, hipSetDevice(p->device));
+    uint32_t range_tile, range_st;
+    ppg_policy_plan_mode(p->direct, p->base, range_tile, range_st);
+    if (r.capacity > p->rows_capacity) {   // (grows only: a call at a smaller capacity lays its plan out inside the same buffer)
+        if (p->rows_plan) (void)hipFree(p->rows_plan);
+        if (p->rows_actions) (void)hipFree(p->rows_actions);
+        p->rows_plan = nullptr; p->rows_actions = nullptr; p->rows_capacity = 0;
+        const size_t words = (size_t)ppgpol::PLAN_HDR + ppg_rows_envs(r.capacity) + ppg_rows_max_tile_words(r.capacity, (uint32_t)p->grid, range_tile, range_st);
+        PPG_POL_TRY(p, hipMalloc((void **)&p->rows_plan, words * 4));
+        PPG_POL_TRY(p, hipMalloc((void **)&p->rows_actions, (size_t)ppg_rows_envs(r.capacity) * PPG_ROWS_CH));
+        p->rows_capacity = r.capacity;
+    }
+    const uint32_t n_envs = ppg_rows_envs(r.capacity);
+    ppgpol::RowsPlanParams L;
+    L.capacity = r.capacity; L.count = r.count; L.count_dev = r.count_dev;
+    L.slots = (uint32_t)p->grid; L.range_tile = range_tile; L.range_st = range_st;
+    L.plan = p->rows_plan;
+    ppgpol::PolParams K = p->base;
+    K.species = 0; K.obs_f32 = r.obs_dtype; K.sample = 0;
+    K.seed_lo = K.seed_hi = 0u; K.seed_dev = nullptr;
+    K.S = K.cap = (int32_t)PPG_ROWS_CH; K.slot0 = 0;
+    K.n_handles = 1; K.n_envs = (int32_t)n_envs;
+    K.env_base[0] = 0;
+    for (int k = 1; k <= ppgpol::MAX_HANDLES; ++k) K.env_base[k] = (int32_t)n_envs;
+    for (int k = 0; k < ppgpol::MAX_HANDLES; ++k) { K.env_state[k] = nullptr; K.obs[k] = nullptr; K.actions[k] = nullptr; }
+    K.obs[0] = (const unsigned char *)r.obs;
+    K.actions[0] = p->rows_actions;
+    K.logits = r.out;
+    K.plan = p->rows_plan;
+    K.tile_env = p->rows_plan + ppgpol::PLAN_HDR + n_envs;
+    const size_t tile_words = ppg_rows_max_tile_words(r.capacity, (uint32_t)p->grid, range_tile, range_st);
+    const size_t items = tile_words > n_envs ? tile_words : (size_t)n_envs;
+    const size_t blocks = (items + 255) / 256;
+    hipLaunchKernelGGL(ppgpol::ppg_policy_plan_rows, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, (hipStream_t)stream, L);
+    return ppg_policy_forward(p, K, stream);
+}
+
+int ppg_policy_rows_plan(const ppg_policy_spec *spec, int32_t slots, int64_t capacity, int64_t count, uint32_t *out,
+                         uint64_t capacity_words, uint64_t *n_words) {
+    if (!spec || !n_words) return ppg_policy_fail(nullptr, PPG_EINVAL, "null argument");
+    int rc = ppg_policy_check_spec(*spec, false);
+    if (rc != PPG_OK) return rc;
+    ppg_policy_layout L;
+    if ((rc = ppg_policy_layout_of(*spec, ppg_pipe_enabled(), L)) != PPG_OK) return rc;
+    uint32_t range_tile, range_st;
+    ppg_policy_plan_mode(L.family != 0, L.K, range_tile, range_st);
+    if (!ppg_rows_plan_cpu(capacity, count, slots, (int32_t)range_tile, (int32_t)range_st, out, capacity_words, n_words))
+        return ppg_policy_fail(nullptr, PPG_EINVAL, "ppg_policy_rows_plan: slots %d / capacity %lld: slots >= 1, capacity in [0, %lld]", slots,
+                               (long long)capacity, (long long)PPG_ROWS_MAX);
     return PPG_OK;
 }
 

@@ -98,7 +98,7 @@ class PolicyNet(torch.nn.Module):
         return self.pi.net.mlp(x.flatten(1))
 
 
-def load_rllib_state_dict(state_dict, obs_range: int = None, obs_channels: int = None) -> PolicyNet:
+def load_rllib_state_dict(state_dict, obs_range: int = None, obs_channels: int = None, head: str = "pi") -> PolicyNet:
     """A `PolicyNet` holding the policy (actor) network of an RLlib PPO RLModule state dict -- what
     `RLModule.from_checkpoint(...)` holds in evaluate_ppo_from_checkpoint_debug.py:129 and greedy actions are taken from at its
     lines 69-96 (`module.get_state()` / the unpickled `module_state.pkl` of a checkpoint; tensors or numpy arrays).
@@ -113,7 +113,19 @@ def load_rllib_state_dict(state_dict, obs_range: int = None, obs_channels: int =
     (up to 256 features).  conv1's input channels and the head's input size decide the reading of the (C,R,R) Box: channels-last
     ("hwc", RLlib: conv1 takes R channels, flat = C * R * cout) or channel-first ("chw": conv1 takes C channels, flat = R * R *
     cout); where both fit, `obs_range` / `obs_channels` decide and channels-last wins otherwise.  Anything else raises ValueError
-    naming the keys and shapes found."""
+    naming the keys and shapes found.
+
+    head="vf" builds the CRITIC instead: the value network as a `PolicyNet(..., n_actions=1)`, whose one "logit" is the value -- what
+    `FusedPolicy.evaluate()` / `AgentTrajectories.values()` run on the matrix cores.  RLlib's keys:
+      conv layers  = encoder.critic_encoder.net.0.cnn.{1,4,7,...}.{weight,bias} (the 4-D weights whose key contains "encoder" and
+                     "critic"); a module built with `vf_share_layers=True` has no critic encoder, and the shared one
+                     (encoder.encoder.net.0.cnn.{1,4,7,...}) is taken;
+      head layers  = vf.net.mlp.{0,2,..}.{weight,bias} (the 2-D weights whose key starts with "vf."; vf.net.mlp.0 alone -- Linear(flat
+                     -> 1) -- in what RLlib builds by default).
+    The tensors land under `PolicyNet`'s names (encoder.actor_encoder..., pi.net.mlp...): the container has one set of names.  The
+    default head="pi" is the actor, as ever."""
+    if head not in ("pi", "vf"):
+        raise ValueError(f"head must be 'pi' (the actor) or 'vf' (the critic), not {head!r}")
     def arr(v):
         return v.detach().cpu().to(torch.float32) if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v), dtype=torch.float32)
     sd = {k: arr(v) for k, v in state_dict.items() if hasattr(v, "shape")}
@@ -128,6 +140,10 @@ def load_rllib_state_dict(state_dict, obs_range: int = None, obs_channels: int =
     head_w = [k for k, v in sd.items() if v.dim() == 2 and k.lower().startswith("pi.")]
     if not head_w:
         head_w = [k for k, v in sd.items() if v.dim() == 2 and "critic" not in k.lower() and not k.lower().startswith("vf")]
+    if head == "vf":   # the critic's own encoder where there is one, else the shared encoder found above; the value head
+        own = [k for k, v in sd.items() if v.dim() == 4 and "encoder" in k.lower() and "critic" in k.lower()]
+        conv_w = own or conv_w
+        head_w = [k for k, v in sd.items() if v.dim() == 2 and k.lower().startswith("vf.")]
     # layer order = the NUMERIC layer indices in the keys (cnn.1, cnn.4, cnn.7, cnn.10), not the dict's order: a state dict that has
     # been sorted or re-serialised lists cnn.1, cnn.10, cnn.4, cnn.7 (tests/golden/rllib_checkpoint/state_listing.json)
     def natural(k):
@@ -360,6 +376,65 @@ class FusedPolicy:
                 raise ValueError(msg)
             raise RuntimeError(f"ppg_policy_act failed ({rc}): {msg}")
         return (lg[0], lg[1]) if want_logits or logits is not None else None
+
+    _ROW_DTYPES = {torch.float64: 0, torch.float32: 1, torch.bfloat16: 2}   # ppg_config.obs_dtype's codes
+
+    def evaluate(self, species, obs, count=None, out=None, stream=None):
+        """The network of `species` (0 predators, 1 prey) over a DENSE tensor of observation rows (`ppg_policy_evaluate`): float32
+        [rows, n_actions], bit for bit what `act(logits=...)` writes for the same observation row and weights -- the same matrix-core
+        kernels behind a plan made from the row count.  What it is for: a critic's values for every stored sample (a critic is a
+        `PolicyNet(..., n_actions=1)`: out[:, 0] is the value; `AgentTrajectories.values()`), and the actor's logits under its current
+        weights after `update()` (`AgentTrajectories.logits()`).
+        obs: a contiguous [rows,C,R,R] tensor, float64 / float32 / bfloat16, on the policy's device -- `store.obs[species]`, or any
+        rows of the species' geometry.  count: None (all rows), an int, or a one-element int64 tensor on the device that the kernel
+        reads when it RUNS (`store.cursor[s:s + 1]`: no read-back); rows [0, min(max(count, 0), rows)) are written, the others keep what
+        they held.  out: caller-owned float32 [rows, n_actions] on the device; without it a tensor zero-filled on the launch stream.
+        Stream-ordered like an `act()`: on one stream with the policy's other calls and behind whatever wrote the rows.  The first
+        call, and every call with more rows than any before, allocates the policy's plan for it; later calls only launch and can be
+        captured.  ValueError, before anything is launched: a closed policy, a species created as None, rows of another geometry,
+        dtype or device, a count or an out of the wrong kind."""
+        if self._closed:
+            raise ValueError("the policy is closed")
+        if species not in (0, 1):
+            raise ValueError(f"species must be 0 (predators) or 1 (prey), not {species!r}")
+        net, h = self.nets[species], self._handles[species]
+        if h is None:
+            raise ValueError(f"the policy was created without a network for species {species}")
+        geometry = (net.obs_channels, net.obs_range, net.obs_range)
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 4 or tuple(obs.shape[1:]) != geometry or obs.dtype not in self._ROW_DTYPES \
+                or obs.device != self.device or not obs.is_contiguous():
+            raise ValueError(f"obs must be a contiguous float64 / float32 / bfloat16 tensor [rows,{geometry[0]},{geometry[1]},{geometry[2]}] "
+                             f"on {self.device}, not {getattr(obs, 'dtype', type(obs))} {list(getattr(obs, 'shape', ()))} on {getattr(obs, 'device', None)}")
+        n = int(obs.shape[0])
+        rows = _abi.PpgPolicyRows()
+        rows.obs, rows.obs_dtype, rows.capacity = obs.data_ptr(), self._ROW_DTYPES[obs.dtype], n
+        if count is None:
+            rows.count = n
+        elif isinstance(count, torch.Tensor):
+            if count.dtype != torch.int64 or count.numel() != 1 or count.device != self.device:
+                raise ValueError("a device-resident count is a one-element int64 tensor on the policy's device")
+            rows.count_dev = count.data_ptr()
+        elif isinstance(count, int) and not isinstance(count, bool):
+            rows.count = min(max(count, -1), n)
+        else:
+            raise ValueError(f"count must be None, an int or a one-element int64 device tensor, not {type(count).__name__}")
+        if out is None:
+            # zero-filled on the stream the kernels run on, so that the fill cannot race with their writes
+            out = _alloc_on(self.device, stream, lambda: torch.zeros((n, net.n_actions), dtype=torch.float32, device=self.device))
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (n, net.n_actions) \
+                or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 tensor [{n},{net.n_actions}] on {self.device}, not "
+                             f"{getattr(out, 'dtype', type(out))} {list(getattr(out, 'shape', ()))} on {getattr(out, 'device', None)}")
+        rows.out = out.data_ptr()
+        s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if stream is None else \
+            C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
+        rc = self._lib.ppg_policy_evaluate(h, C.byref(rows), s)
+        if rc != 0:
+            msg = self._lib.ppg_policy_last_error(h).decode()
+            if rc == -1:
+                raise ValueError(msg)
+            raise RuntimeError(f"ppg_policy_evaluate failed ({rc}): {msg}")
+        return out
 
     def close(self):
         for h in self._handles:

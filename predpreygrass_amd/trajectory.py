@@ -86,6 +86,11 @@ the bits of scatter() -> returns_and_gae() -> flat() -> .float() (kept verbatim 
     count, mean, std = traj.advantage_moments(stats)                # float64 [2] each, no read-back
     adv_n = (adv[PREY] - mean[PREY]) / (std[PREY] + 1e-8)           # the usual value target: adv[PREY] + v_prey
 
+The values themselves come from the store without a torch forward when the critic is a `FusedPolicy` of `PolicyNet(..., n_actions=1)`
+networks: `v = traj.values(critic)` runs the policy kernels over `store.obs` (`FusedPolicy.evaluate()`, `ppg_policy_evaluate`: the row
+count is read from `store.cursor` on the device) and `traj.targets(v[0][:n_pred], v[1][:n_prey], ...)` takes them;
+`traj.logits(fused, s)` is the same for the actor's logits under its current weights.
+
 and the minibatch step of the learner closes the loop: PPO's clipped loss (RLlib's `compute_loss_for_module`) and its gradients from those
 columns and the learner's fresh logits and values, in two launches (`env.ppo_loss()`, `ppg_ppo_loss`, csrc/ppg_ppo.h), nothing read back:
 
@@ -334,6 +339,36 @@ class AgentTrajectories:
         n = int(st.cursor[species].item())
         return (st.logp[species][:n], None if st.entropy is None else st.entropy[species][:n],
                 None if st.dist is None else st.dist[species][:n])
+
+    def logits(self, fused, species, out=None):
+        """The outputs of `fused`'s network of one species (0 predators, 1 prey) over the stored samples, under its CURRENT weights:
+        float32 [capacity_s, A_s] with row k = the network's logits for the observation in slot k -- bit for bit what `act()` would
+        write for that row (`FusedPolicy.evaluate()`, `ppg_policy_evaluate`: the matrix-core kernels over `store.obs[species]`).
+        After `fused.update()` this is the learner's view of every sample without a torch forward: KL against `behaviour()`'s dist,
+        early stopping, offline greedy evaluation.  The count is `store.cursor[species]`, read by the kernel on the device: nothing is
+        read back; rows at and behind it keep what they held (zeros in a tensor the call allocates).  Stream-ordered like an act."""
+        self._need_store("logits")
+        st = self.store
+        return fused.evaluate(species, st.obs[species], count=st.cursor[species:species + 1], out=out)
+
+    def values(self, critic):
+        """(v_pred, v_prey): a critic's value of every stored sample, float32 [capacity_s] per species (None for a species the critic
+        has no network for), v[s][k] = the value of the observation in slot k.  critic: a `FusedPolicy` of `PolicyNet(...,
+        n_actions=1)` networks (`load_rllib_state_dict(..., head="vf")`), whose one output is the value -- evaluated by the policy
+        kernels over the store (`logits()`), no float32 torch forward over millions of rows, nothing read back.  What targets() takes:
+
+            v = traj.values(critic)
+            adv, ret, stats = traj.targets(v[0][:n_pred], v[1][:n_prey], 0.99, 0.95)      # n_s = traj.samples(s)[0]"""
+        self._need_store("values")
+        out = []
+        for s, net in enumerate(critic.nets):
+            if net is None:
+                out.append(None)
+                continue
+            if net.n_actions != 1:
+                raise ValueError(f"a critic is a network with n_actions = 1 (its output is the value); species {s} has {net.n_actions}")
+            out.append(self.logits(critic, s).squeeze(-1))
+        return tuple(out)
 
     def scatter(self, x_pred, x_prey, fill=0.0):
         """The inverse of flat(): a [len,B,S] tensor with x_s[k] at the (t, b, r) of sample k of species s and `fill` everywhere else --
