@@ -371,3 +371,4 @@ static int backend_launch(ppg_handle *h, int mode, const ppg::KParams &P, void *
 
 // policy inference next to the env (MFMA kernels + their host side)
 #include "ppg_policy.h"
+#include "ppg_policy_host.h"

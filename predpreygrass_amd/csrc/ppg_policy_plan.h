@@ -32,18 +32,16 @@ constexpr int PPG_PLAN_HDR = 3;           // words in front of the prefix sums (
 // ---- part 1: what plan_body and ppg_policy_plan_rows decide alike ----
 
 // TILE MODE.  As many whole ROUNDS of 128-sample tiles as the resident workgroups (slots) can be given, then ONE last round in which the
-// remaining samples are spread over the slots in tiles of 32 / 64 / 96 / 128 (ppg_policy.h: plan_body says why).  force_ts: experiments,
-// every tile that size.
+// remaining samples are spread over the slots in tiles of 32 / 64 / 96 / 128 (ppg_policy.h: plan_body says why).
 struct ppg_plan_tiles {
     uint32_t n_full, ts;
 };
-PPG_PLAN_HD inline ppg_plan_tiles ppg_plan_tiles_of(uint32_t all, uint32_t slots, uint32_t force_ts) {
+PPG_PLAN_HD inline ppg_plan_tiles ppg_plan_tiles_of(uint32_t all, uint32_t slots) {
     const uint32_t per_round = PPG_PLAN_TILE * slots;
-    uint32_t n_full = (all / per_round) * slots;
+    const uint32_t n_full = (all / per_round) * slots;
     const uint32_t rest = all - n_full * PPG_PLAN_TILE;
     uint32_t ts = 32u * ((rest + 32u * slots - 1u) / (32u * slots));   // 32 * ceil(rest / (32 * slots))
     if (ts < 32u) ts = 32u;
-    if (force_ts) { ts = force_ts; n_full = 0; }
     return {n_full, ts};
 }
 PPG_PLAN_HD inline uint32_t ppg_plan_tile_count(uint32_t all, uint32_t n_full, uint32_t ts) {
@@ -112,7 +110,7 @@ PPG_PLAN_HD inline ppg_rows_shape ppg_rows_shape_of(int64_t capacity, int64_t co
         s.w1 = r.share; s.w2 = r.tpw;
         s.tile_words = slots * r.tpw;
     } else {
-        const ppg_plan_tiles t = ppg_plan_tiles_of(s.all, slots, 0u);
+        const ppg_plan_tiles t = ppg_plan_tiles_of(s.all, slots);
         s.w1 = t.n_full; s.w2 = t.ts;
         s.tile_words = ppg_plan_tile_count(s.all, t.n_full, t.ts);
     }
