@@ -965,6 +965,58 @@ int ppg_policy_evaluate(ppg_policy *p, const ppg_policy_rows *rows, void *stream
 int ppg_policy_rows_plan(const ppg_policy_spec *spec, int32_t slots, int64_t capacity, int64_t count, uint32_t *out,
                          uint64_t capacity_words, uint64_t *n_words);
 
+/* ---- the policy networks' training pass: minibatch forward and backward in float32 -----------------------------------------
+ * ppg_net_forward and ppg_net_backward run a network of the shapes ppg_policy_create_spec accepts (anything else: PPG_EINVAL with
+ * the same words) over a minibatch of M rows taken from a dense [capacity][C][R][R] observation tensor through an int32 slot index,
+ * forwards (one launch) and backwards (two launches), in float32 throughout -- the learner's side of a PPO step, where ppg_policy_act
+ * and ppg_policy_evaluate are the actor's (bf16 operands).  A critic is the same network with n_actions == 1.  csrc/ppg_net.h.
+ *   Weights  the weight pointers of `spec` are DEVICE pointers, float32, contiguous, PyTorch layouts, exactly as ppg_policy_update takes
+ *            them: the parameters where the optimiser keeps them, read when the kernels run.  No packed copy exists.
+ *   Rows     k = index ? index[i] : i.  A row with 0 <= k < capacity (compared before k becomes an address) reads observation row k,
+ *            float64 and bfloat16 converted to float32 as obs.to(torch.float32) does.  Any other row is a SELECTION: nothing of it is
+ *            read (no observation, not its grad_out row), its out row is +0.0, and it adds nothing to any gradient.
+ *   Tiles    a workgroup (256 threads) takes tiles of TS consecutive minibatch rows (TS = 4, 2 or 1: the largest with two buffers of
+ *            TS x the widest layer in 80 KB of LDS, else 1).  Workgroups are persistent: G = groups ? min(groups, tiles) :
+ *            min(tiles, 1024), workgroup g takes tiles g, g + G, ...
+ *   Forward  every convolution (zero pad 1, 3x3, stride 1, bias, ReLU) and every linear layer (ReLU on all but the last) with the
+ *            tile's activations in LDS; out[M][n_actions] float32; every post-ReLU activation goes to `workspace`, which the
+ *            backward call of the same batch reads.  A chain starts from the bias (convolutions) or from +0.0 with the bias added
+ *            last (linear layers), products enter by fmaf.
+ *   Backward launch 1, per tile, from grad_out[M][n_actions]: the ReLU mask is activation > 0; per layer the tile's contribution to
+ *            every weight and bias gradient (one fmaf chain over the tile's rows ascending, then positions ascending) is stored
+ *            (first tile of the workgroup) or added (later tiles, ascending) into partial[g][n_params].  Launch 2 adds the G rows in
+ *            ascending g and writes the gradients through the pointers of `grads` (a ppg_policy_spec of which only the weight
+ *            pointers are read: Conv2d.weight [cout][cin][3][3], Linear.weight [out][in], the biases).  No atomics: for a given M
+ *            and G the gradients are the same bits from run to run.  `partial` needs no initial value.
+ *   Order    of the parameters in partial's rows (and in a flat gradient buffer a caller lays its `grads` pointers over):
+ *            conv0.weight, conv0.bias, conv1.weight, ..., fc0.weight, fc0.bias, ...
+ * ppg_net_bytes needs no device and does not read the weight pointers: out[0] = bytes of the workspace for M rows, out[1] = bytes
+ * of partial (G rows), out[2] = n_params, out[3] = TS.  PPG_EINVAL: spec or out NULL, a network outside the set, M outside
+ * [1, 2^24], groups < 0 (the text: ppg_last_error(NULL)).
+ * PPG_EINVAL (text in ppg_last_error beginning "ppg_net_forward:" / "ppg_net_backward:", nothing is launched, nothing written): spec or
+ * mb NULL; obs (with capacity > 0), out (forward) or workspace NULL; grad_out, grads or partial NULL; a NULL weight (gradient) pointer of a
+ * layer the shape has; M outside [1, 2^24]; capacity outside [0, INT32_MAX]; groups < 0; an obs_dtype other than 0 / 1 / 2;
+ * workspace_bytes / partial_bytes smaller than ppg_net_bytes says; a network outside the set.
+ * The handle supplies the device, the stream ordering and the error text only.  All three calls are asynchronous on `stream`,
+ * allocate nothing and can be captured in a graph (a network whose tile needs more than 64 KB of LDS -- ppg_net_bytes' TS x the widest layer x 8
+ * bytes -- has the kernel's limit raised by a host call at its FIRST launch on a device: run that launch uncaptured once).  `mb` of ppg_net_backward must be the batch of the forward call that filled
+ * the workspace. */
+typedef struct ppg_net_batch {
+    const void *obs;          /* device, dense [capacity][C][R][R], element type obs_dtype */
+    int32_t obs_dtype;        /* 0 float64, 1 float32, 2 bfloat16 */
+    int32_t groups;           /* 0: automatic; otherwise the number of workgroups G (at most the number of tiles, at most 1024) */
+    int64_t capacity;         /* rows of obs, 0 .. INT32_MAX */
+    const int32_t *index;     /* [M] slot of minibatch row i, or NULL: k = i */
+    int64_t M;                /* minibatch rows, 1 .. 2^24 */
+    float *out;               /* [M][n_actions]; not looked at by ppg_net_backward */
+    float *workspace;         /* the activations, workspace_bytes >= ppg_net_bytes' out[0] */
+    uint64_t workspace_bytes;
+} ppg_net_batch;
+int ppg_net_bytes(const ppg_policy_spec *spec, int64_t M, int32_t groups, uint64_t out[4]);
+int ppg_net_forward(ppg_handle *h, const ppg_policy_spec *spec, const ppg_net_batch *mb, void *stream);
+int ppg_net_backward(ppg_handle *h, const ppg_policy_spec *spec, const ppg_net_batch *mb, const float *grad_out,
+                     const ppg_policy_spec *grads, float *partial, uint64_t partial_bytes, void *stream);
+
 /* A device buffer for the caller-owned observation tensors whose physical pages are picked at random from a stretch of device
  * memory `spread` times its size (HIP virtual memory management: spread x as many 2 MB chunks are created, a random subset is
  * mapped in random order, the rest is given back at once).  Optional -- any device pointer works as obs_pred / obs_prey -- but where

@@ -205,6 +205,13 @@ class PpgPolicyRows(C.Structure):
                 ("count_dev", C.c_void_p), ("out", C.c_void_p)]
 
 
+class PpgNetBatch(C.Structure):
+    """include/ppg.h: struct ppg_net_batch (one minibatch of observation rows for ppg_net_forward / ppg_net_backward)."""
+    _fields_ = [("obs", C.c_void_p), ("obs_dtype", C.c_int32), ("groups", C.c_int32), ("capacity", C.c_int64), ("index", C.c_void_p),
+                ("M", C.c_int64), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
+
+
+NET_SYMBOLS = ["ppg_net_bytes", "ppg_net_forward", "ppg_net_backward"]
 SPREAD_SYMBOLS = ["ppg_alloc_spread", "ppg_free_spread", "ppg_spread_stats", "ppg_spread_last_error"]   # HIP library only, like the policy symbols
 EXPORTED_SYMBOLS = [
     "ppg_abi_version", "ppg_create", "ppg_destroy", "ppg_get_buffers", "ppg_reset", "ppg_reset_from_state", "ppg_observe", "ppg_step", "ppg_step_many",
@@ -212,7 +219,7 @@ EXPORTED_SYMBOLS = [
     "ppg_get_wave_plan", "ppg_rebalance", "ppg_set_resident_envs", "ppg_get_resident_envs",
     "ppg_export_grid", "ppg_walls_changed", "ppg_state_bytes", "ppg_export_state", "ppg_import_state", "ppg_pack_bytes", "ppg_pack",
     "ppg_fetch_bytes", "ppg_fetch", "ppg_link", "ppg_record", "ppg_record_obs", "ppg_record_logp", "ppg_backward",
-    "ppg_backward_samples", "ppg_ppo_loss", "ppg_lexkey", "ppg_lds_bytes", "ppg_step_kernel_name", "ppg_last_error",
+    "ppg_backward_samples", "ppg_ppo_loss", *NET_SYMBOLS, "ppg_lexkey", "ppg_lds_bytes", "ppg_step_kernel_name", "ppg_last_error",
 ] + POLICY_SYMBOLS + SPREAD_SYMBOLS
 
 
@@ -292,6 +299,13 @@ def bind(lib: C.CDLL) -> C.CDLL:
                                          C.c_void_p]   # st, tg, dtype, gamma, lam, stream
     lib.ppg_ppo_loss.restype = C.c_int
     lib.ppg_ppo_loss.argtypes = [C.c_void_p, C.POINTER(PpgPpoBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]   # h, mb, three outputs, stream
+    lib.ppg_net_bytes.restype = C.c_int
+    lib.ppg_net_bytes.argtypes = [C.POINTER(PpgPolicySpec), C.c_int64, C.c_int32, C.POINTER(C.c_uint64 * 4)]
+    lib.ppg_net_forward.restype = C.c_int
+    lib.ppg_net_forward.argtypes = [C.c_void_p, C.POINTER(PpgPolicySpec), C.POINTER(PpgNetBatch), C.c_void_p]
+    lib.ppg_net_backward.restype = C.c_int
+    lib.ppg_net_backward.argtypes = [C.c_void_p, C.POINTER(PpgPolicySpec), C.POINTER(PpgNetBatch), C.c_void_p,   # h, spec, mb, grad_out
+                                     C.POINTER(PpgPolicySpec), C.c_void_p, C.c_uint64, C.c_void_p]   # grads, partial, its bytes, stream
     if hasattr(lib, "ppg_alloc_spread"):
         lib.ppg_alloc_spread.restype = C.c_int
         lib.ppg_alloc_spread.argtypes = [C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]

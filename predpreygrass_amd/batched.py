@@ -74,6 +74,23 @@ def _ptr(x):
     return None if x is None else C.c_void_p(x.data_ptr())
 
 
+def net_grad_offsets(net):
+    """Element offsets of a `policy.PolicyNet`'s parameters in the flat gradient buffer of net_backward(): conv0.weight, conv0.bias, ...,
+    fc0.weight, fc0.bias, ... (include/ppg.h), and behind them the total."""
+    offsets = [0]
+    for m in net.conv + net.fc:
+        for p in (m.weight, m.bias):
+            offsets.append(offsets[-1] + p.numel())
+    return offsets
+
+
+def net_grad_views(net, flat):
+    """[(parameter, view of `flat` of its shape)] in the order of net_grad_offsets()."""
+    offsets = net_grad_offsets(net)
+    params = [p for m in net.conv + net.fc for p in (m.weight, m.bias)]
+    return [(p, flat[o:o + p.numel()].view(p.shape)) for p, o in zip(params, offsets)]
+
+
 class BatchedPredPreyGrass:
     """Tensor API.
 
@@ -722,6 +739,99 @@ class BatchedPredPreyGrass:
         self._check(self._lib.ppg_ppo_loss(self._handle, C.byref(mb), _ptr(grad_logits), _ptr(grad_values), _ptr(partial),
                                            self._stream(stream)), "ppg_ppo_loss", value_error=True)
         return grad_logits, grad_values, partial
+
+    # ------------------------------------------------------------------
+    # the policy networks' training pass (`ppg_net_forward` / `ppg_net_backward`, include/ppg.h; csrc/ppg_net.h)
+    _OBS_DTYPES = {torch.float64: 0, torch.float32: 1, torch.bfloat16: 2}
+
+    def _net_spec(self, net, what="parameter"):
+        """`ppg_policy_spec` of a `policy.PolicyNet` whose parameters the kernels read in place: float32, contiguous, on the env's device."""
+        from .policy import FusedPolicy   # (policy imports this module)
+        names = {id(p): n for n, p in net.named_parameters()}
+        return FusedPolicy._spec(net, lambda p: self._tensor_arg(f"{what} {names.get(id(p), '?')}", p, (torch.float32,), tuple(p.shape)).value)
+
+    @staticmethod
+    def _net_grad_spec(net, base):
+        """The `grads` argument of ppg_net_backward: net's shape with pointers into a flat float32 buffer at address `base`."""
+        from .policy import FusedPolicy
+        offsets = iter(net_grad_offsets(net))
+        return FusedPolicy._spec(net, lambda p: base + 4 * next(offsets))
+
+    def net_bytes(self, net, M, groups=0):
+        """(workspace bytes, partial bytes, n_params, TS) of net_forward() / net_backward() for a minibatch of M rows (`ppg_net_bytes`: no
+        device involved).  The flat gradient buffer holds conv0.weight, conv0.bias, ..., fc0.weight, fc0.bias, ... in that order."""
+        from .policy import FusedPolicy
+        out = (C.c_uint64 * 4)()
+        shape = FusedPolicy._spec(net, lambda p: None)   # (the weight pointers are not read: the net may live anywhere)
+        rc = self._lib.ppg_net_bytes(C.byref(shape), int(M), int(groups), C.byref(out))
+        if rc != 0:
+            raise ValueError(self._lib.ppg_last_error(None).decode())
+        return tuple(int(x) for x in out)
+
+    def _net_batch(self, net, obs, index, M, groups, out, workspace):
+        """The `ppg_net_batch` both calls take, after the checks both make."""
+        if obs.dim() != 4 or tuple(obs.shape[1:]) != (net.obs_channels, net.obs_range, net.obs_range):
+            raise ValueError(f"obs must be [capacity,{net.obs_channels},{net.obs_range},{net.obs_range}], not {tuple(obs.shape)}")
+        mb = _abi.PpgNetBatch()
+        mb.obs = self._tensor_arg("obs", obs, tuple(self._OBS_DTYPES), tuple(obs.shape)).value
+        mb.obs_dtype, mb.capacity, mb.groups = self._OBS_DTYPES[obs.dtype], int(obs.shape[0]), int(groups)
+        if index is not None:
+            if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1:
+                raise ValueError(f"index must be an int32 tensor [M] (the slot words of the store), not {getattr(index, 'dtype', type(index))}")
+            mb.index = self._tensor_arg("index", index, (torch.int32,), (int(index.shape[0]),)).value
+        mb.M = int(M if M is not None else index.shape[0] if index is not None else obs.shape[0])
+        if index is not None and mb.M != index.shape[0]:
+            raise ValueError(f"M = {mb.M}, but index has {index.shape[0]} rows")
+        if out is not None:   # (backward writes no out)
+            mb.out = self._tensor_arg("out", out, (torch.float32,), (mb.M, net.n_actions)).value
+        if workspace.dim() != 1:
+            raise ValueError(f"workspace must be a flat float32 tensor, not {tuple(workspace.shape)}")
+        mb.workspace = self._tensor_arg("workspace", workspace, (torch.float32,), (None,)).value
+        mb.workspace_bytes = workspace.numel() * 4
+        return mb
+
+    def net_forward(self, net, obs, index=None, M=None, groups=0, out=None, workspace=None, stream=None):
+        """`net`'s float32 forward pass over the minibatch rows `obs[index]` in ONE launch (`ppg_net_forward`, include/ppg.h: rows, tiles
+        and the arithmetic are stated there).  net: a `policy.PolicyNet` whose parameters are float32 on the env's device (they are
+        read where they lie, when the kernel runs); obs: contiguous [capacity,C,R,R] float64 / float32 / bfloat16; index: int32 [M] or
+        None (rows 0 .. M - 1; M defaults to the capacity).  A row whose slot is outside [0, capacity) gets +0.0 and nothing of it is
+        read.  groups: 0, or the number of workgroups (tests, A/B runs).
+        Returns (out float32 [M,n_actions], workspace): the flat float32 tensor of activations that net_backward() of the same
+        minibatch reads -- both newly allocated unless given.
+        stream (optional): as in backward() -- the launch and the allocations go to that stream."""
+        rows = int(M if M is not None else index.shape[0] if isinstance(index, torch.Tensor) else obs.shape[0])
+        need = self.net_bytes(net, rows, groups)
+        out, workspace = _alloc_on(self.device, stream, lambda: (
+            torch.empty((rows, net.n_actions), dtype=torch.float32, device=self.device) if out is None else out,
+            torch.empty((need[0] // 4,), dtype=torch.float32, device=self.device) if workspace is None else workspace))
+        mb = self._net_batch(net, obs, index, rows, groups, out, workspace)
+        self._check(self._lib.ppg_net_forward(self._handle, C.byref(self._net_spec(net)), C.byref(mb), self._stream(stream)),
+                    "ppg_net_forward", value_error=True)
+        return out, workspace
+
+    def net_backward(self, net, obs, index, grad_out, workspace, M=None, groups=0, grads=None, partial=None, stream=None):
+        """The gradients of `net`'s parameters for d loss / d out = grad_out, in TWO launches (`ppg_net_backward`): per workgroup partial
+        sums without atomics, then their sum in a fixed order -- the same bits from run to run.  obs, index, M, groups and workspace:
+        those of the net_forward() call whose activations `workspace` holds; grad_out float32 [M,n_actions] (rows that are selections
+        are not read).  grads: a flat float32 tensor [n_params] to write into, partial: a flat float32 tensor of net_bytes()[1] / 4
+        elements -- both newly allocated unless given.  Returns (grads, partial); `net_grad_views(net, grads)` are the per-parameter
+        views, in the order conv0.weight, conv0.bias, ..., fc0.weight, fc0.bias, ...
+        stream (optional): as in net_forward()."""
+        rows = int(M if M is not None else index.shape[0] if isinstance(index, torch.Tensor) else obs.shape[0])
+        need = self.net_bytes(net, rows, groups)
+        grads, partial = _alloc_on(self.device, stream, lambda: (
+            torch.empty((need[2],), dtype=torch.float32, device=self.device) if grads is None else grads,
+            torch.empty((need[1] // 4,), dtype=torch.float32, device=self.device) if partial is None else partial))
+        mb = self._net_batch(net, obs, index, rows, groups, None, workspace)
+        g = self._tensor_arg("grad_out", grad_out, (torch.float32,), (rows, net.n_actions))
+        base = self._tensor_arg("grads", grads, (torch.float32,), (need[2],)).value
+        if partial.dim() != 1:
+            raise ValueError(f"partial must be a flat float32 tensor, not {tuple(partial.shape)}")
+        part = self._tensor_arg("partial", partial, (torch.float32,), (None,))
+        gspec = self._net_grad_spec(net, base)
+        self._check(self._lib.ppg_net_backward(self._handle, C.byref(self._net_spec(net)), C.byref(mb), g, C.byref(gspec), part,
+                                               partial.numel() * 4, self._stream(stream)), "ppg_net_backward", value_error=True)
+        return grads, partial
 
     def export_grid(self):
         """grid_world_state of every env: float64 [B,4,G,G] (predpreygrass_rllib_env.py:124)."""

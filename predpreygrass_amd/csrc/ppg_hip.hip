@@ -238,7 +238,7 @@ static int backend_rebalance(ppg_handle *h, int weight_pred, int weight_prey, vo
 
 // ---- the learner-side kernels: one wavefront per workgroup, the parameter block by value ----------------------------------------
 // ppg_pack / ppg_fetch / ppg_link / ppg_record / ppg_record_obs / ppg_record_logp / ppg_backward / ppg_backward_samples / ppg_ppo_loss
-// (ppg_pack.h, ppg_fetch.h, ppg_link.h, ppg_record.h, ppg_obs_store.h, ppg_logp.h, ppg_backward.h, ppg_ppo.h)
+// (the four-wave kernels of ppg_net_forward / ppg_net_backward stand further down) (ppg_pack.h, ppg_fetch.h, ppg_link.h, ppg_record.h, ppg_obs_store.h, ppg_logp.h, ppg_backward.h, ppg_ppo.h)
 #define PPG_ROWS_KERNEL(name, Params, main, lds_bytes)                                         \
     extern "C" __global__ void __launch_bounds__(64) name(const ppg::Params K) {              \
         __shared__ __attribute__((aligned(16))) unsigned char lds[lds_bytes];                  \
@@ -291,6 +291,44 @@ static int backend_backward_samples(ppg_handle *h, const ppg::BackwardSamplesPar
 static int backend_ppo_loss(ppg_handle *h, const ppg::PpoParams &K, void *stream) {
     if (int rc = backend_launch_rows(h, ppg_ppo_count, K.G, K, stream)) return rc;
     return backend_launch_rows(h, ppg_ppo_rows, K.G, K, stream);
+}
+
+
+// ---- ppg_net_forward / ppg_net_backward (ppg_net.h): four-wave workgroups, dynamic LDS (two activation buffers of a tile) ------------
+extern "C" __global__ void __launch_bounds__(ppg::NET_THREADS) ppg_net_fwd(const ppg::NetParams K) {
+    PPG_DYNAMIC_LDS(lds);
+    ppg::net_forward_main(*PPG_KERNARG_PTR(ppg::NetParams, K), lds);
+}
+extern "C" __global__ void __launch_bounds__(ppg::NET_THREADS) ppg_net_bwd(const ppg::NetParams K) {
+    PPG_DYNAMIC_LDS(lds);
+    ppg::net_backward_main(*PPG_KERNARG_PTR(ppg::NetParams, K), lds);
+}
+extern "C" __global__ void __launch_bounds__(ppg::NET_THREADS) ppg_net_reduce(const ppg::NetParams K) {
+    ppg::net_reduce_main(*PPG_KERNARG_PTR(ppg::NetParams, K));
+}
+
+// which: 0 forward, 1 backward, 2 reduce.  More than 64 KB of dynamic LDS has to be allowed per kernel and device: done the first time a
+// launch needs more than was allowed so far (a host call, remembered here), never again for that size -- a warmed launch only launches.
+static int backend_net_launch(ppg_handle *h, int which, int grid, const ppg::NetParams &K, int lds_bytes, void *stream) {
+    static void (*const kernels[3])(const ppg::NetParams) = {ppg_net_fwd, ppg_net_bwd, ppg_net_reduce};
+    static int allowed[3][64];   // bytes allowed so far, per kernel and device (0: the default 64 KB)
+    void (*kernel)(const ppg::NetParams) = kernels[which];
+    if (int rc = backend_use_device(h)) return rc;
+    int &have = allowed[which][h->device & 63];
+    if (lds_bytes > 64 * 1024 && lds_bytes > have) {
+        PPG_HIP_TRY(h, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        have = 160 * 1024;
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(ppg::NET_THREADS), (size_t)lds_bytes, (hipStream_t)stream, K);
+    PPG_HIP_TRY(h, hipGetLastError());
+    return PPG_OK;
+}
+static int backend_net_forward(ppg_handle *h, const ppg::NetParams &K, int lds_bytes, void *stream) {
+    return backend_net_launch(h, 0, K.G, K, lds_bytes, stream);
+}
+static int backend_net_backward(ppg_handle *h, const ppg::NetParams &K, int lds_bytes, void *stream) {
+    if (int rc = backend_net_launch(h, 1, K.G, K, lds_bytes, stream)) return rc;
+    return backend_net_launch(h, 2, (K.n_params + ppg::NET_THREADS - 1) / ppg::NET_THREADS, K, 0, stream);
 }
 
 static int backend_copy(ppg_handle *h, void *dst, const void *src, size_t bytes, bool to_device, void *stream) {

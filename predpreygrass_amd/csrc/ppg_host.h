@@ -25,6 +25,8 @@
 #include "ppg_obs_store.h"
 #include "ppg_logp.h"
 #include "ppg_ppo.h"
+#include "ppg_net.h"
+#include "ppg_policy_shape.h"
 
 // How a handle's step is scheduled (never what it computes): wavefronts per workgroup, the row count from which helper wavefronts
 // stay, and -- cooperative kernels -- how many envs share a workgroup (0 = one env per workgroup, the ppg[w]_step kernels).
@@ -546,7 +548,8 @@ static int backend_pack(ppg_handle *h, const ppg::PackParams &K, void *stream);
 static int backend_fetch(ppg_handle *h, const ppg::FetchParams &K, void *stream);
 static void backend_free(ppg_handle *h, void *p);
 // the launches of ppg_link (ppg_link.h), ppg_record (ppg_record.h), ppg_record_obs (ppg_obs_store.h: two), ppg_record_logp
-// (ppg_logp.h: two), ppg_backward and ppg_backward_samples (ppg_backward.h), ppg_ppo_loss (ppg_ppo.h: two)
+// (ppg_logp.h: two), ppg_backward and ppg_backward_samples (ppg_backward.h), ppg_ppo_loss (ppg_ppo.h: two), ppg_net_forward (ppg_net.h:
+// one launch of K.G workgroups of NET_THREADS threads with lds_bytes of dynamic LDS) and ppg_net_backward (two)
 static int backend_link(ppg_handle *h, const ppg::LinkParams &K, void *stream);
 static int backend_record(ppg_handle *h, const ppg::RecordParams &K, void *stream);
 static int backend_record_obs(ppg_handle *h, const ppg::ObsStoreParams &K, void *stream);
@@ -554,6 +557,8 @@ static int backend_record_logp(ppg_handle *h, const ppg::LogpParams &K, void *st
 static int backend_backward(ppg_handle *h, const ppg::BackwardParams &K, void *stream);
 static int backend_backward_samples(ppg_handle *h, const ppg::BackwardSamplesParams &K, void *stream);
 static int backend_ppo_loss(ppg_handle *h, const ppg::PpoParams &K, void *stream);
+static int backend_net_forward(ppg_handle *h, const ppg::NetParams &K, int lds_bytes, void *stream);
+static int backend_net_backward(ppg_handle *h, const ppg::NetParams &K, int lds_bytes, void *stream);
 #ifdef PPG_WAVE_EMU
 // CPU test build (tests/wave_emu): `grid` one-wave workgroups of Main with exactly LDS bytes each, as on the device.  These seven
 // launches stand here, not next to the test backend's backend_pack / backend_fetch: a revision's test suite is also run against
@@ -590,6 +595,19 @@ static int backend_backward_samples(ppg_handle *, const ppg::BackwardSamplesPara
 static int backend_ppo_loss(ppg_handle *, const ppg::PpoParams &K, void *) {
     ppg_emu_rows<ppg::PpoParams, ppg::ppo_count_main>(K, K.G);
     return ppg_emu_rows<ppg::PpoParams, ppg::ppo_rows_main, ppg::PPO_LDS_BYTES>(K, K.G);
+}
+// (four-wave workgroups with exactly lds_bytes of LDS each)
+static int backend_net_forward(ppg_handle *, const ppg::NetParams &K, int lds_bytes, void *) {
+    for (int b = 0; b < K.G; ++b)
+        wv::run_block([](void *arg) { ppg::net_forward_main(*(const ppg::NetParams *)arg, wv::emu().lds); }, (void *)&K, b, (size_t)lds_bytes, ppg::NET_WAVES);
+    return PPG_OK;
+}
+static int backend_net_backward(ppg_handle *, const ppg::NetParams &K, int lds_bytes, void *) {
+    for (int b = 0; b < K.G; ++b)
+        wv::run_block([](void *arg) { ppg::net_backward_main(*(const ppg::NetParams *)arg, wv::emu().lds); }, (void *)&K, b, (size_t)lds_bytes, ppg::NET_WAVES);
+    for (int b = 0; b < (K.n_params + ppg::NET_THREADS - 1) / ppg::NET_THREADS; ++b)
+        wv::run_block([](void *arg) { ppg::net_reduce_main(*(const ppg::NetParams *)arg); }, (void *)&K, b, 16, ppg::NET_WAVES);
+    return PPG_OK;
 }
 #endif
 
@@ -1457,6 +1475,92 @@ int ppg_ppo_loss(ppg_handle *h, const ppg_ppo_batch *mb, float *grad_logits, flo
     K.vf_clip = mb->vf_clip; K.vf_coeff = mb->vf_coeff; K.ent_coeff = mb->ent_coeff; K.kl_coeff = mb->kl_coeff;
     K.grad_logits = grad_logits; K.grad_values = grad_values; K.partial = partial;
     return backend_ppo_loss(h, K, stream);
+}
+
+// ---- ppg_net_*: the geometry a network's shape decides (device-free), the argument checks, the launches ------------------------------
+// The checks in front of ppg::net_layout (ppg_net.h): K's geometry for M rows and `groups` workgroups (0: automatic); *lds_bytes: dynamic
+// LDS of a workgroup.
+// PPG_EINVAL with the reason in msg[256].
+static int ppg_net_layout(const ppg_policy_spec &sp, int64_t M, int32_t groups, ppg::NetParams &K, int *lds_bytes, char *msg) {
+    memset(&K, 0, sizeof K);
+    if (int rc = ppg_policy_shape_check(sp, false, msg, 256)) return rc;
+    if (M < 1 || M > (1 << 24)) return ppg_policy_shape_fail(msg, 256, "M = %lld outside [1, 2^24]", (long long)M);
+    if (groups < 0) return ppg_policy_shape_fail(msg, 256, "groups = %d is negative", groups);
+    *lds_bytes = ppg::net_layout(sp, M, groups, K);
+    return PPG_OK;
+}
+
+static void ppg_net_sizes(const ppg::NetParams &K, uint64_t out[4]) {
+    out[0] = (uint64_t)K.M * (uint64_t)K.ws_row * 4; out[1] = (uint64_t)K.G * (uint64_t)K.n_params * 4;
+    out[2] = (uint64_t)K.n_params; out[3] = (uint64_t)K.TS;
+}
+
+int ppg_net_bytes(const ppg_policy_spec *spec, int64_t M, int32_t groups, uint64_t out[4]) {
+    if (!spec || !out) return ppg_fail(nullptr, PPG_EINVAL, "ppg_net_bytes: spec or out is NULL");
+    ppg::NetParams K;
+    int lds = 0;
+    char msg[256];
+    if (ppg_net_layout(*spec, M, groups, K, &lds, msg) != PPG_OK) return ppg_fail(nullptr, PPG_EINVAL, "ppg_net_bytes: %s", msg);
+    ppg_net_sizes(K, out);
+    return PPG_OK;
+}
+
+// what ppg_net_forward and ppg_net_backward check alike, and the parameter block both launch with
+static int ppg_net_params(ppg_handle *h, const char *fn, bool forward, const ppg_policy_spec *spec, const ppg_net_batch *mb, ppg::NetParams &K,
+                          int *lds_bytes) {
+    if (!spec) return ppg_fail(h, PPG_EINVAL, "%s: spec is NULL", fn);
+    if (!mb) return ppg_fail(h, PPG_EINVAL, "%s: mb is NULL", fn);
+    char msg[256];
+    if (ppg_net_layout(*spec, mb->M, mb->groups, K, lds_bytes, msg) != PPG_OK) return ppg_fail(h, PPG_EINVAL, "%s: %s", fn, msg);
+    if (ppg_policy_shape_check(*spec, true, msg, sizeof msg) != PPG_OK) return ppg_fail(h, PPG_EINVAL, "%s: %s", fn, msg);
+    if (mb->capacity < 0 || mb->capacity > INT32_MAX)
+        return ppg_fail(h, PPG_EINVAL, "%s: capacity = %lld outside [0, INT32_MAX]", fn, (long long)mb->capacity);
+    if (mb->obs_dtype < 0 || mb->obs_dtype > 2) return ppg_fail(h, PPG_EINVAL, "%s: unknown obs_dtype %d", fn, mb->obs_dtype);
+    if (!mb->obs && mb->capacity > 0) return ppg_fail(h, PPG_EINVAL, "%s: obs of ppg_net_batch is NULL", fn);
+    if (forward && !mb->out) return ppg_fail(h, PPG_EINVAL, "%s: out of ppg_net_batch is NULL", fn);
+    if (!mb->workspace) return ppg_fail(h, PPG_EINVAL, "%s: workspace of ppg_net_batch is NULL", fn);
+    uint64_t need[4];
+    ppg_net_sizes(K, need);
+    if (mb->workspace_bytes < need[0])
+        return ppg_fail(h, PPG_EINVAL, "%s: workspace_bytes = %llu, %lld rows need %llu", fn, (unsigned long long)mb->workspace_bytes,
+                        (long long)mb->M, (unsigned long long)need[0]);
+    K.capacity = mb->capacity; K.obs_dtype = mb->obs_dtype; K.obs = mb->obs; K.index = mb->index;
+    K.out = mb->out; K.workspace = mb->workspace;
+    for (int l = 0; l < spec->n_conv; ++l) { K.conv_w[l] = spec->conv_w[l]; K.conv_b[l] = spec->conv_b[l]; }
+    for (int l = 0; l < spec->n_fc; ++l) { K.fc_w[l] = spec->fc_w[l]; K.fc_b[l] = spec->fc_b[l]; }
+    return PPG_OK;
+}
+
+int ppg_net_forward(ppg_handle *h, const ppg_policy_spec *spec, const ppg_net_batch *mb, void *stream) {
+    if (!h) return PPG_EINVAL;
+    ppg::NetParams K;
+    int lds = 0;
+    if (int rc = ppg_net_params(h, "ppg_net_forward", true, spec, mb, K, &lds)) return rc;
+    return backend_net_forward(h, K, lds, stream);
+}
+
+int ppg_net_backward(ppg_handle *h, const ppg_policy_spec *spec, const ppg_net_batch *mb, const float *grad_out,
+                     const ppg_policy_spec *grads, float *partial, uint64_t partial_bytes, void *stream) {
+    if (!h) return PPG_EINVAL;
+    const char *fn = "ppg_net_backward";
+    ppg::NetParams K;
+    int lds = 0;
+    if (int rc = ppg_net_params(h, fn, false, spec, mb, K, &lds)) return rc;
+    if (!grad_out) return ppg_fail(h, PPG_EINVAL, "%s: grad_out is NULL", fn);
+    if (!grads) return ppg_fail(h, PPG_EINVAL, "%s: grads is NULL", fn);
+    if (!partial) return ppg_fail(h, PPG_EINVAL, "%s: partial is NULL", fn);
+    uint64_t need[4];
+    ppg_net_sizes(K, need);
+    if (partial_bytes < need[1])
+        return ppg_fail(h, PPG_EINVAL, "%s: partial_bytes = %llu, %d workgroups of %d parameters need %llu", fn,
+                        (unsigned long long)partial_bytes, K.G, K.n_params, (unsigned long long)need[1]);
+    int seg = 0;
+    for (int l = 0; l < spec->n_conv; ++l) { K.grad[seg++] = (float *)grads->conv_w[l]; K.grad[seg++] = (float *)grads->conv_b[l]; }
+    for (int l = 0; l < spec->n_fc; ++l) { K.grad[seg++] = (float *)grads->fc_w[l]; K.grad[seg++] = (float *)grads->fc_b[l]; }
+    for (int q = 0; q < seg; ++q)
+        if (!K.grad[q]) return ppg_fail(h, PPG_EINVAL, "%s: a gradient pointer of grads is NULL", fn);
+    K.grad_out = grad_out; K.partial = partial;
+    return backend_net_backward(h, K, lds, stream);
 }
 
 #ifdef PPG_PROFILE_PHASES

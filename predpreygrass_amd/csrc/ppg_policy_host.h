@@ -4,6 +4,7 @@
 #pragma once
 
 #include "ppg_policy.h"
+#include "ppg_policy_shape.h"
 
 struct ppg_policy {
     int32_t device, R, n_actions, layout, cin;
@@ -192,31 +193,11 @@ static bool ppg_pipe_layout_at(int C, int R, int P, int blk, int f_elems, int ta
 }
 
 // The shape rules of ppg_policy_create_spec, device-free: shared with ppg_policy_describe so that the description of a network exists
-// exactly when the network can be created.  need_weights: also require the weight pointers.
+// exactly when the network can be created.  need_weights: also require the weight pointers.  (The rules themselves:
+// ppg_policy_shape.h, which ppg_net_* share.)
 static int ppg_policy_check_spec(const ppg_policy_spec &sp, bool need_weights) {
-    const int layout = sp.layout, R = sp.obs_range, n_actions = sp.n_actions, C = sp.obs_channels;
-    if (layout != PPG_POLICY_LAYOUT_CHW && layout != PPG_POLICY_LAYOUT_HWC) return ppg_policy_fail(nullptr, PPG_EINVAL, "unknown layout %d", layout);
-    if (sp.flatten != PPG_POLICY_FLATTEN_NCHW && sp.flatten != PPG_POLICY_FLATTEN_NHWC) return ppg_policy_fail(nullptr, PPG_EINVAL, "unknown flatten order %d", sp.flatten);
-    if (R < 1 || R > 15) return ppg_policy_fail(nullptr, PPG_EINVAL, "obs_range %d outside 1..15", R);
-    if (C < 1 || C > 8) return ppg_policy_fail(nullptr, PPG_EINVAL, "obs_channels %d outside 1..8", C);
-    if (n_actions < 1 || n_actions > 32) return ppg_policy_fail(nullptr, PPG_EINVAL, "n_actions %d outside 1..32", n_actions);
-    if (sp.n_conv < 1 || sp.n_conv > PPG_POLICY_MAX_CONV) return ppg_policy_fail(nullptr, PPG_EINVAL, "n_conv %d outside 1..%d", sp.n_conv, PPG_POLICY_MAX_CONV);
-    if (sp.n_fc < 1 || sp.n_fc > PPG_POLICY_MAX_FC) return ppg_policy_fail(nullptr, PPG_EINVAL, "n_fc %d outside 1..%d", sp.n_fc, PPG_POLICY_MAX_FC);
-    for (int l = 0; l < sp.n_conv; ++l) {
-        const int lim = l == 0 ? 16 : l == 1 ? 32 : 64;
-        if (sp.conv_out[l] < 1 || sp.conv_out[l] > lim)
-            return ppg_policy_fail(nullptr, PPG_EINVAL, "convolution %d has %d output channels: the kernels take up to 16 / 32 / 64 / 64 ...", l + 1, sp.conv_out[l]);
-        if (need_weights && (!sp.conv_w[l] || !sp.conv_b[l])) return ppg_policy_fail(nullptr, PPG_EINVAL, "a convolution weight pointer is NULL");
-    }
-    for (int l = 0; l < sp.n_fc; ++l) {
-        if (need_weights && (!sp.fc_w[l] || !sp.fc_b[l])) return ppg_policy_fail(nullptr, PPG_EINVAL, "a linear weight pointer is NULL");
-        if (l + 1 < sp.n_fc && (sp.fc_out[l] < 1 || sp.fc_out[l] > 256))
-            return ppg_policy_fail(nullptr, PPG_EINVAL, "hidden head layer %d has %d features: the kernels take up to 256", l + 1, sp.fc_out[l]);
-    }
-    if (sp.fc_out[sp.n_fc - 1] != n_actions) return ppg_policy_fail(nullptr, PPG_EINVAL, "the last linear layer has %d outputs, n_actions is %d", sp.fc_out[sp.n_fc - 1], n_actions);
-    if (sp.n_fc > 1 && sp.n_conv != 3) return ppg_policy_fail(nullptr, PPG_EINVAL, "a head with hidden layers needs exactly three convolutions (found %d)", sp.n_conv);
-    if (sp.n_fc > 1 && layout != PPG_POLICY_LAYOUT_HWC && C != 4)
-        return ppg_policy_fail(nullptr, PPG_EINVAL, "channel-first networks with hidden head layers read 4-channel rows (found %d)", C);
+    char msg[256];
+    if (ppg_policy_shape_check(sp, need_weights, msg, sizeof msg) != PPG_OK) return ppg_policy_fail(nullptr, PPG_EINVAL, "%s", msg);
     return PPG_OK;
 }
 

@@ -102,6 +102,13 @@ columns and the learner's fresh logits and values, in two launches (`env.ppo_los
 
 Samples whose action is still ACTION_UNSET or whose logp is still NaN are skipped, so an index over all slots is legal.
 `ppo_loss_function()` is the same behind `loss.backward()`, `ppo_loss_torch()` the same loss as torch ops.
+
+The network on either side of that loss runs on the device too: `NetLearner(env, net, max_rows)` is `net(obs[index.long()])` as one
+launch and its backward as two (`env.net_forward()` / `env.net_backward()`, `ppg_net_forward` / `ppg_net_backward`, csrc/ppg_net.h:
+float32, no atomics), attached to autograd, and `traj.forward(learner, PREY, index)` applies it to the store:
+
+    actor, critic = NetLearner(env, prey_net, 128), NetLearner(env, prey_critic, 128)
+    logits, values = traj.forward(actor, PREY, index), traj.forward(critic, PREY, index)[:, 0]
 """
 from __future__ import annotations
 
@@ -110,7 +117,7 @@ import types
 import torch
 
 from . import _abi
-from .batched import capture_graph
+from .batched import capture_graph, net_grad_views
 
 
 class ObservationStore:
@@ -614,6 +621,13 @@ class AgentTrajectories:
         n = advantage.shape[0]
         return st.action[species][:n], st.logp[species][:n], None if st.dist is None else st.dist[species][:n], adv_norm
 
+    def forward(self, learner, species, index=None):
+        """`learner(store.obs[species], index)`: a `NetLearner`'s output for the samples in slots `index` (int32 [M]; None: every row of
+        the store's tensor), float32 [M,n_out] attached to its network's parameters -- the logits of an actor; a critic's values are
+        column 0."""
+        self._need_store("forward")
+        return learner(self.store.obs[species], index)
+
     def ppo_loss(self, species, logits, values, index, advantage, value_target, *, clip=0.3, vf_clip=10.0, vf_coeff=1.0, ent_coeff=0.0,
                  kl_coeff=0.2, adv_norm=None):
         """(loss, stats, grad_logits, grad_values): PPO's clipped loss of one minibatch of one species -- the mean over the valid
@@ -745,6 +759,91 @@ class _StatsSink:
         result = self.traj.ppo_loss(*args, **kw)
         self.out["stats"] = result[1]
         return result
+
+
+class _NetForward(torch.autograd.Function):
+    """NetLearner's two calls as one node of the autograd graph of the network's parameters."""
+
+    @staticmethod
+    def forward(ctx, learner, obs, index, *params):
+        out = learner._forward(obs, index, pending=True)
+        ctx.learner, ctx.token, ctx.obs, ctx.index = learner, learner._pending, obs, index
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return (None, None, None, *ctx.learner._backward(ctx.token, ctx.obs, ctx.index, grad_out))
+
+
+class NetLearner:
+    """A `policy.PolicyNet`'s minibatch forward and backward on the device in three launches (`env.net_forward()` / `env.net_backward()`,
+    `ppg_net_forward` / `ppg_net_backward`, csrc/ppg_net.h: float32, no atomics), in place of `net(obs[index.long()])` and its autograd
+    graph of a dozen modules -- the parameters are read where the optimiser keeps them, so an `optimizer.step()` needs no hand-over.
+
+        learner = NetLearner(env, actor, max_rows=4096)
+        logits = learner(traj.store.obs[s], index)          # float32 [M,A], attached to actor's parameters
+        loss, stats = ppo_loss_function(traj, s, logits, values, index, adv, ret); loss.backward(); optimizer.step()
+
+    net: its parameters float32 and contiguous on the env's device.  The learner owns the activation workspace and the partial sums
+    for up to max_rows rows, and `grads`, a flat float32 buffer of every parameter's gradient (conv0.weight, conv0.bias, ...,
+    fc0.weight, fc0.bias, ...) with the per-parameter views `grad_views`; the backward pass hands those views to autograd, which adds
+    them into `p.grad` (`torch.autograd.backward([logits], [grad_logits])` and `loss.backward()` alike).  A critic is a net with
+    n_actions = 1: its values are `learner(obs, index)[:, 0]`.
+    One forward's activations live in the workspace until its backward has run: a second forward in between raises RuntimeError
+    (`release()` gives up a forward whose backward will never come); so does a backward after a parameter was changed in place, as
+    autograd's own saved tensors would.  With autograd disabled (`torch.no_grad()`) a call only
+    evaluates and holds nothing.  groups: 0, or the number of workgroups of both calls."""
+
+    def __init__(self, env, net, max_rows, groups=0):
+        self.env, self.net, self.max_rows, self.groups = env, net, int(max_rows), int(groups)
+        need = env.net_bytes(net, self.max_rows, self.groups)
+        self.tile_rows = need[3]
+        dev = env.device
+        self.workspace = torch.empty((need[0] // 4,), dtype=torch.float32, device=dev)
+        self.partial = torch.empty((need[1] // 4,), dtype=torch.float32, device=dev)
+        self.grads = torch.zeros((need[2],), dtype=torch.float32, device=dev)
+        views = net_grad_views(net, self.grads)
+        self._params = [p for p, _ in views]
+        self.grad_views = [v for _, v in views]   # (kept: autograd copies a gradient somebody else still holds instead of adopting it)
+        self._pending = None
+        self._calls = 0
+
+    def _rows(self, obs, index):
+        M = int(index.shape[0] if index is not None else obs.shape[0])
+        if M > self.max_rows:
+            raise ValueError(f"{M} rows, but the learner was built for max_rows = {self.max_rows}")
+        return M
+
+    def _forward(self, obs, index, pending):
+        if self._pending is not None:
+            raise RuntimeError("NetLearner: a second forward before the backward of the first would overwrite its activations "
+                               "(run the backward pass, or release() the pending forward)")
+        out, _ = self.env.net_forward(self.net, obs, index, M=self._rows(obs, index), groups=self.groups, workspace=self.workspace)
+        if pending:
+            self._calls += 1
+            self._pending = self._calls
+            self._versions = [p._version for p in self._params]
+        return out
+
+    def _backward(self, token, obs, index, grad_out):
+        if token != self._pending:
+            raise RuntimeError("NetLearner: the activations of this forward are gone (a backward ran already, or release())")
+        if [p._version for p in self._params] != self._versions:   # (the kernels read the parameters when they run, as autograd's saved tensors)
+            raise RuntimeError("NetLearner: a parameter was changed in place between the forward and its backward; the stored "
+                               "activations belong to the old weights (run the backward before optimizer.step(), or release())")
+        self.env.net_backward(self.net, obs, index, grad_out.contiguous(), self.workspace, M=self._rows(obs, index), groups=self.groups,
+                              grads=self.grads, partial=self.partial)
+        self._pending = None
+        return self.grad_views
+
+    def release(self):
+        """Forget a forward whose backward will not run."""
+        self._pending = None
+
+    def __call__(self, obs, index=None):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self._params):
+            return _NetForward.apply(self, obs, index, *self._params)
+        return self._forward(obs, index, pending=False)
 
 
 class GraphedCollector:
