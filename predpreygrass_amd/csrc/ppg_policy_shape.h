@@ -1,5 +1,5 @@
 // ppg_policy_shape.h -- the shape rules of a ppg_policy_spec, device-free and free of the policy kernels: ppg_policy_create_spec /
-// ppg_policy_describe (ppg_policy_host.h) and ppg_net_* (ppg_host.h, also in the CPU test build) accept the same networks and refuse
+// ppg_policy_describe (ppg_policy_host.h) and ppg_net_* (ppg_learner_host.h, also in the CPU test build) accept the same networks and refuse
 // the others with the same words.
 #pragma once
 

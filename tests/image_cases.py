@@ -611,7 +611,7 @@ def fetch_matrix(bk, gid, src):
     fresh = fresh_copy(bk, gid, src)
     small = check_fetch(fresh, gid, state, 0, 1, f"{gid} fresh handle, fetch(0, 1)")
     large = fetch_reference(state, gid, 0, B)
-    hint = small.used + small.used // 4 + 4096   # (ppg_host.h: what the next call copies in its first transfer, at least the fixed part)
+    hint = small.used + small.used // 4 + 4096   # (ppg_learner_host.h: what the next call copies in its first transfer, at least the fixed part)
     assert large.used > max(hint, large.fixed), "the large image must not fit the first transfer"
     check_fetch(fresh, gid, state, 0, B, f"{gid} fresh handle, fetch(0, {B}) after fetch(0, 1)")
     check_fetch(fresh, gid, state, 0, 1, f"{gid} fresh handle, fetch(0, 1) again")

@@ -98,7 +98,7 @@ static int backend_launch(ppg_handle *h, int mode, const ppg::KParams &P, void *
     return PPG_OK;
 }
 
-// (ppg_emu_rows and the launches of the later learner-side calls: ppg_host.h)
+// (ppg_emu_rows and the launches of the later learner-side calls: ppg_learner_host.h)
 static int backend_pack(ppg_handle *, const ppg::PackParams &K, void *) {
     ppg_emu_rows<ppg::PackParams, ppg::pack_scan_main, ppg::ROWS_SCAN_LDS_BYTES>(K, 1);
     return ppg_emu_rows<ppg::PackParams, ppg::pack_rows_main>(K, K.n_envs);
